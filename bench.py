@@ -8,6 +8,11 @@ One "step" = the reference's SFT step (examples/ft_bloom.py:84-90): forward (24-
 shifted cross entropy) -> zero_grad -> backward -> AdamW(lr=1e-5, wd=0.01), on a synthetic batch B=8, S=1024 per GPU
 (weak scaling), bf16 compute with fp32 master weights / gradients / optimizer state.  Inputs are resident in HBM
 before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line; --full adds every secondary measurement (host enqueue
+time, shader clocks and rocm-smi power, the live LM-head roofline, the per-class breakdown, the padded sample, the exposed
+collective time at N > 1, the eager twin of --graph, the CPU baseline).  --dump-outputs DIR writes what the last timed step
+computed (dump_outputs).
 """
 import argparse
 import json
@@ -26,6 +31,12 @@ import torch.distributed as dist
 V, H, L, NH = 250880, 1024, 24, 16
 PEAK_BF16_TFLOPS = 2500.0          # MI355X dense bf16 MFMA peak (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0
+DUMP_LOGITS = 1 << 20              # --dump-outputs: logits sampled from the last timed step
+DUMP_PER_PARAM = 4096              # --dump-outputs: elements sampled from every parameter and its gradient (all of a smaller one)
+
+
+def _round(x, n):
+    return None if x is None else round(x, n)
 
 
 def flops_per_token(S: int) -> float:
@@ -147,6 +158,32 @@ def build_model(device, compute_dtype):
     return m.train()
 
 
+def dump_outputs(path, loss, logits, model):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files under `path` (~10 MB at the headline shape).
+    loss.npy [1]; logits_sample.npy: DUMP_LOGITS logits at seeded (batch, position, vocab) indices (absent under --graph: a replay
+    returns the loss only); params_sample.npy / grads_sample.npy: the weights after the optimizer step and the gradients of that
+    step at the same seeded DUMP_PER_PARAM elements of every parameter, in named_parameters() order.  The indices depend only on
+    the shapes, so two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    if logits is not None:
+        g = torch.Generator().manual_seed(4321)
+        b, s, v = (torch.randint(0, n, (DUMP_LOGITS,), generator=g).to(logits.device) for n in logits.shape)
+        arrays["logits_sample"] = logits.detach()[b, s, v].float()
+    g = torch.Generator().manual_seed(8765)
+    ps, gs = [], []
+    for _, p in model.named_parameters():
+        n = p.numel()
+        i = (torch.randint(0, n, (DUMP_PER_PARAM,), generator=g) if n > DUMP_PER_PARAM else torch.arange(n)).to(p.device)
+        ps.append(p.detach().reshape(-1)[i].float())
+        gs.append(p.grad.detach().reshape(-1)[i].float() if p.grad is not None else torch.full((i.numel(),), float("nan"), device=p.device))
+    arrays["params_sample"] = torch.cat(ps)
+    arrays["grads_sample"] = torch.cat(gs)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def _cpu_model() -> str:
     try:
         for line in open("/proc/cpuinfo"):
@@ -234,7 +271,14 @@ def main(argv=None):
     ap.add_argument("--graph", action="store_true",
                     help="N = 1: replay the captured step from a hipGraph (cleantransformer_amd/graph.py) instead of issuing it launch by launch; measured "
                          "equal on the GPU-bound headline shape (profiles/r06_launch_floor.txt), so the default stays the reference's eager loop")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (host enqueue, clocks and power, LM-head roofline, breakdown, padded sample, "
+                         "exposed collectives, --graph's eager twin, CPU baseline); off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; see dump_outputs)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -268,6 +312,7 @@ def main(argv=None):
     labels = ids.clone()
     batch = {"ids": ids, "am": am, "labels": labels}
     holder = {"net": model}
+    last = {"keep": False, "logits": None}                                  # --dump-outputs: the logits of the last timed step
 
     scaler = None
     if args.dtype == "fp16":
@@ -292,6 +337,8 @@ def main(argv=None):
             return graphed(batch["ids"], batch["am"], batch["labels"])
         outputs, _ = holder["net"](input_ids=batch["ids"], attention_mask=batch["am"], labels=batch["labels"])
         loss = outputs[0]
+        if last["keep"]:
+            last["logits"] = outputs[1]
         opt.zero_grad()
         if scaler is not None:
             scaler.scale(loss).backward()
@@ -370,8 +417,9 @@ def main(argv=None):
         args.ddp_backend = chosen[0]
         holder["net"] = wrap(*chosen)
 
-    def timed_steps(n):
+    def timed_steps(n, keep_last=False):
         """n steps between barrier + synchronize brackets; per-step device time from HIP events on the compute stream.
+        keep_last: the last step leaves its logits in last["logits"].
         -> (wall seconds of the bracketed region, per-step milliseconds, host loop seconds, last loss)"""
         torch.cuda.synchronize()
         if world > 1:
@@ -381,8 +429,10 @@ def main(argv=None):
         t0 = time.perf_counter()
         ev[0].record()
         for i in range(n):
+            last["keep"] = keep_last and i == n - 1
             loss_ = step()
             ev[i + 1].record()
+        last["keep"] = False
         host = time.perf_counter() - t0                                      # host loop time inside the timed region (back-pressured)
         torch.cuda.synchronize()
         if world > 1:
@@ -393,26 +443,33 @@ def main(argv=None):
 
     for _ in range(args.warmup):
         loss = step()
-    # host cost of enqueueing one step, measured with an EMPTY device queue (two steps right after a synchronize: the host is
-    # never held back by the GPU).  Inside the timed region below the host runs ahead of the device until the HIP queue pushes
-    # back, so its loop time there converges to the GPU step time and says nothing about the host.
-    torch.cuda.synchronize()
-    h0 = time.perf_counter()
-    for _ in range(2):
-        loss = step()
-    host_enqueue_ms = (time.perf_counter() - h0) / 2 * 1e3
-    smi_before = _smi_snapshot() if rank == 0 else None
-    clock_before = ops.clock_probe(device)                                 # shader clock under MFMA load, chip warm from the warm-up steps
+    host_enqueue_ms = smi_before = clock_before = clock_after = smi_after = None
     timer = ops.KernelTimer(["lm_head_fwd"])
-    if graphed is None:
-        ops.set_timer(timer)
-    dt, per_step_ms, host_loop_s, loss = timed_steps(args.steps)
+    if args.full:
+        # host cost of enqueueing one step, measured with an EMPTY device queue (two steps right after a synchronize: the host is
+        # never held back by the GPU).  Inside the timed region below the host runs ahead of the device until the HIP queue pushes
+        # back, so its loop time there converges to the GPU step time and says nothing about the host.
+        torch.cuda.synchronize()
+        h0 = time.perf_counter()
+        for _ in range(2):
+            loss = step()
+        host_enqueue_ms = (time.perf_counter() - h0) / 2 * 1e3
+        smi_before = _smi_snapshot() if rank == 0 else None
+        clock_before = ops.clock_probe(device)                             # shader clock under MFMA load, chip warm from the warm-up steps
+        if graphed is None:
+            ops.set_timer(timer)
+    dt, per_step_ms, host_loop_s, loss = timed_steps(args.steps, keep_last=args.dump_outputs is not None)
     ops.set_timer(None)
+    if args.dump_outputs is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, loss, last["logits"], model)
+        last["logits"] = None
     graph_info = None
     if graphed is not None:
+        graph_info = {"enabled": graphed.graph is not None, "replays": graphed.replays, "fallback_reason": graphed.fallback_reason}
+    if graphed is not None and args.full:
         # the same step issued launch by launch, right after the timed region: the eager number beside the replayed one, and the HIP-event brackets
         # of the LM-head forward (roofline.largest_launch) — a replay runs no host code that could record them
-        graph_info = {"enabled": graphed.graph is not None, "replays": graphed.replays, "fallback_reason": graphed.fallback_reason}
         graphed.enabled = False
         for _ in range(2):
             step()
@@ -427,15 +484,17 @@ def main(argv=None):
                 step()
     # package power / shader clock while stepping: sampled beside `steps` EXTRA steps right after the timed region, not inside it — ten rocm-smi
     # processes per second beside the timed steps cost 0.07 ms per step (same box, three interleaved pairs: 36.60 vs 36.54; round-4 advisor)
-    sampler = _PowerSampler().start() if (rank == 0 and not args.no_power_sampler) else None
-    if not args.no_power_sampler:
+    sample_power = args.full and not args.no_power_sampler
+    sampler = _PowerSampler().start() if (rank == 0 and sample_power) else None
+    if sample_power:
         for _ in range(max(args.steps, 10)):
             step()
         torch.cuda.synchronize()
     if sampler is not None:
         sampler.stop()
-    clock_after = ops.clock_probe(device)                                  # ... and right after the timed steps
-    smi_after = _smi_snapshot() if rank == 0 else None
+    if args.full:
+        clock_after = ops.clock_probe(device)                              # ... and right after the timed steps
+        smi_after = _smi_snapshot() if rank == 0 else None
     final_loss = float(loss.detach())
     bad_loss = not (math.isfinite(final_loss) and 0.0 < final_loss < 2.0 * math.log(V))
     if world > 1:                                                         # every rank leaves together (a lone exit would hang the others in the next all-reduce)
@@ -460,7 +519,7 @@ def main(argv=None):
     # chunked tied-table gradient and its row scatter still run): exposed_ms = step with collectives - step without.  After the timed
     # region and after the loss check — those steps train on unaveraged gradients.
     comm_exposed = None
-    if world > 1 and isinstance(holder["net"], DDP):
+    if args.full and world > 1 and isinstance(holder["net"], DDP):
         holder["net"].stub_collectives = True
         try:
             for _ in range(2):
@@ -479,7 +538,7 @@ def main(argv=None):
 
     # ---- per-class device time of one step (HIP-event brackets inside the library; side stream off so that brackets do not overlap)
     breakdown = None
-    if not args.no_breakdown:
+    if args.full and not args.no_breakdown:
         if graphed is not None:
             graphed.enabled = False                                      # the per-class brackets are recorded by host code: eager steps
         side = modeling_bloom._WGRAD_SIDE_STREAM
@@ -504,7 +563,7 @@ def main(argv=None):
 
     # ---- secondary sample (SURVEY §8(d) "Synthetic inputs"): 25 % of every row right-padded
     padded = None
-    if not args.no_padded_sample:
+    if args.full and not args.no_padded_sample:
         am_p = am.clone()
         am_p[:, (S * 3) // 4:] = 0
         batch["am"] = am_p
@@ -544,15 +603,15 @@ def main(argv=None):
                        "padded_sample": padded},
             "graph": graph_info if graph_info is not None else {"enabled": False, "why": "eager loop (default); --graph replays the captured step at N = 1"},
             "timing": {"value_from": "median of the per-step HIP-event times of the timed steps (max over ranks)",
-                       "eager_ms_per_step": None if graph_info is None else graph_info["eager_ms_per_step"],
+                       "eager_ms_per_step": None if graph_info is None else graph_info.get("eager_ms_per_step"),
                        "ms_per_step_median": round(med_ms, 3), "ms_per_step_mean_wall": round(mean_ms, 3),
                        "ms_per_step_min": round(min(per_step_ms), 3), "ms_per_step_max": round(max(per_step_ms), 3),
                        "wall_s_timed_region": round(dt, 4),
-                       "shader_clock_mhz_before": round(clock_before, 1), "shader_clock_mhz_after": round(clock_after, 1),
+                       "shader_clock_mhz_before": _round(clock_before, 1), "shader_clock_mhz_after": _round(clock_after, 1),
                        "shader_clock_note": "ctmi_clock_probe: s_memtime / s_memrealtime of one wave while 2048 workgroups issue bf16 MFMAs (~6 ms), "
                                             "launched right before / right after the timed region; the 2.5 PF peak assumes 2400 MHz",
                        "smi_before": smi_before, "smi_after": smi_after, "power_while_stepping": sampler.summary() if sampler is not None else None},
-            "final_loss": round(final_loss, 4), "host_enqueue_ms_per_step": round(host_enqueue_ms, 2),
+            "final_loss": round(final_loss, 4), "host_enqueue_ms_per_step": _round(host_enqueue_ms, 2),
             "host_loop_ms_per_step_in_timed_region": round(host_loop_s / args.steps * 1e3, 2),
             # the step-level fraction — algorithmic FLOPs of the whole step (6 N_mm + 6 L S H per token, attention
             # causal-half) over the step time, against the dense bf16 MFMA peak.  The largest single launch is a sub-entry.
@@ -565,10 +624,10 @@ def main(argv=None):
                                             "achieved": round(head_tflops, 1), "frac": round(head_tflops / PEAK_BF16_TFLOPS, 4),
                                             "avg_launch_ms": round(head_avg, 4), "launches": len(head_ms),
                                             "traffic_bytes_per_launch": _profiled_traffic(),
-                                            "algorithmic_bytes_per_launch": 2.0 * (B * S * H + V * H + B * S * V)},
+                                            "algorithmic_bytes_per_launch": 2.0 * (B * S * H + V * H + B * S * V)} if args.full else None,
                          "breakdown_ms_per_step": breakdown},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline)
         print(json.dumps(out), flush=True)
     if world > 1:

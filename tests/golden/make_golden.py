@@ -37,6 +37,21 @@ from CleanTransformer import optimizer as ref_opt
 from CleanTransformer.models import modeling_bloom as rb
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+PART_BYTES = 960 * 1024                                # raw bytes per part: every committed file stays below 1 MiB
+
+
+def savez_parts(name, out):
+    """np.savez_compressed of `out` as NAME.npz, NAME.part2.npz, ... with at most PART_BYTES of arrays each (tests/golden_npz.py reads them)."""
+    parts, cur, size = [], {}, 0
+    for k, v in out.items():
+        v = np.asarray(v)
+        if cur and size + v.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k], size = v, size + v.nbytes
+    parts.append(cur)
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(HERE, name + (".npz" if i == 0 else f".part{i + 1}.npz")), **p)
 
 
 def det_init(model):
@@ -259,7 +274,7 @@ def gen_tiny():
     gen = m3.generate(p_ids, attention_mask=p_am,
                       generation_configs=dict(beam_size=1, max_gen_len=6, do_sample=False, end_ids=None, pad_id=3))
     out.update(greedy_prompt=npy(p_ids), greedy_mask=npy(p_am), greedy_out=npy(gen))
-    np.savez_compressed(os.path.join(HERE, "tiny_bloom.npz"), **out)
+    savez_parts("tiny_bloom", out)
     print("tiny: sha", sha[:16], "ids", ids_sha[:16], "traj", rec)
     return sha, ids_sha
 
@@ -368,7 +383,7 @@ def gen_gpt():
     gen = m.generate(p_ids, attention_mask=torch.ones(2, 7, dtype=torch.long),
                      generation_configs=dict(beam_size=1, max_gen_len=6, do_sample=False, end_ids=None, pad_id=3))
     out.update(greedy_prompt=npy(p_ids), greedy_out=npy(gen))
-    np.savez_compressed(os.path.join(HERE, "tiny_gpt.npz"), **out)
+    savez_parts("tiny_gpt", out)
 
 
 # ---------------------------------------------------------------------------------------

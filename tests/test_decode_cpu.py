@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import cpu_kernel_emulation as emu
+import golden_npz
 from oracle import bloom_ref as R
 from oracle import decode_ref as D
 from oracle import gpt_ref as GR
@@ -92,7 +93,7 @@ def test_oracle_gpt_beam_search_matches_reference():
     pos, seg = T(DEC["gpt_pos"]), T(DEC["gpt_seg"])
     same(D.greedy_ngram(step, ids, am, 6, 0, position_ids=pos, segment_ids=seg), DEC["gpt_greedy_posseg"])
     same(D.beam_search(step, 2, ids, am, 3, 6, [GPTS[0] + 1], pad_id=3, position_ids=pos, segment_ids=seg), DEC["gpt_beam3_posseg"])
-    assert not np.array_equal(DEC["gpt_greedy_posseg"], np.load(os.path.join(G, "tiny_gpt.npz"))["greedy_out"])   # the ids do matter
+    assert not np.array_equal(DEC["gpt_greedy_posseg"], golden_npz.load("tiny_gpt")["greedy_out"])   # the ids do matter
 
 
 # ------------------------------------------------------------------------------------------------ 2. product host logic

@@ -10,11 +10,12 @@ import pytest
 import torch
 
 import cpu_kernel_emulation as emu
+import golden_npz
 from oracle import gpt_ref as GR
 from oracle.bloom_ref import AdamState
 
 G = os.path.join(os.path.dirname(__file__), "golden")
-GPT = np.load(os.path.join(G, "tiny_gpt.npz"))
+GPT = golden_npz.load("tiny_gpt")
 
 
 def T(a):

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
+
 pytestmark = pytest.mark.gpu
 
 from oracle import bloom_ref as R  # noqa: E402
@@ -19,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 G = os.path.join(HERE, "golden")
 DEV = "cuda:0"
-TINY = np.load(os.path.join(G, "tiny_bloom.npz"))
+TINY = golden_npz.load("tiny_bloom")
 
 
 def T(a):
@@ -200,7 +202,7 @@ def test_tiny_left_padding_uniform_rows():
     gn = gnorm(m)
     assert abs(gn - float(TINY["lp_gnorm"])) <= 1e-4 * gn
     named = dict(m.named_parameters())
-    for k in TINY.files:
+    for k in TINY:
         if k.startswith("lp_g_"):
             close(k, named[k[5:]].grad, TINY[k], 2e-4, 2e-7)
 
@@ -861,7 +863,7 @@ def test_bench_two_rank_code_path_executes():
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join("tests", "bench_plumbing.py"), "2,4096", "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "2", "--seq", "256", "--comm-dtype", "bf16"],
+                        "--batch", "2", "--seq", "256", "--comm-dtype", "bf16", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -11,12 +11,14 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 
 pytestmark = pytest.mark.gpu
-TINY = np.load(os.path.join(HERE, "golden", "tiny_bloom.npz"))
+TINY = golden_npz.load("tiny_bloom")
 
 
 def _T(a):

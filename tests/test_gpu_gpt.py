@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 from oracle import gpt_ref as GR  # noqa: E402
@@ -15,7 +17,7 @@ from oracle import gpt_ref as GR  # noqa: E402
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 G = os.path.join(HERE, "golden")
-GPT = np.load(os.path.join(G, "tiny_gpt.npz"))
+GPT = golden_npz.load("tiny_gpt")
 
 
 def T(a):

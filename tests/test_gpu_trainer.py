@@ -7,12 +7,14 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-TINY = np.load(os.path.join(HERE, "golden", "tiny_bloom.npz"))
+TINY = golden_npz.load("tiny_bloom")
 V, H, L, NH, B, S = [int(v) for v in TINY["cfg"]]
 
 

@@ -9,10 +9,11 @@ import pytest
 import torch
 
 import cpu_kernel_emulation as emu
+import golden_npz
 from oracle import bloom_ref as R
 
 G = os.path.join(os.path.dirname(__file__), "golden")
-TINY = np.load(os.path.join(G, "tiny_bloom.npz"))
+TINY = golden_npz.load("tiny_bloom")
 OPS = np.load(os.path.join(G, "ops.npz"))
 
 
@@ -82,7 +83,7 @@ def test_left_padding_and_post_ln_switch(monkeypatch):
     close(logits, TINY["lp_logits"], 1e-5, 1e-6)
     loss.backward()
     named = dict(m.named_parameters())
-    for k in TINY.files:
+    for k in TINY:
         if k.startswith("lp_g_"):
             close(named[k[5:]].grad, TINY[k], 1e-4, 1e-7)
     # apply_residual_connection_post_layernorm=True branch vs the oracle

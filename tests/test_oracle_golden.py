@@ -8,11 +8,13 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
+
 from oracle import bloom_ref as R
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 OPS = np.load(os.path.join(G, "ops.npz"))
-TINY = np.load(os.path.join(G, "tiny_bloom.npz"))
+TINY = golden_npz.load("tiny_bloom")
 
 
 def T(a):
@@ -199,7 +201,7 @@ def test_tiny_left_padding_uniform_rows():
     close(loss, TINY["lp_loss"], 1e-6, 0)
     close(logits, TINY["lp_logits"], 1e-5, 1e-6)
     assert abs(R.grad_norm(grads.values()) - float(TINY["lp_gnorm"])) < 1e-5 * float(TINY["lp_gnorm"])
-    for k in TINY.files:
+    for k in TINY:
         if k.startswith("lp_g_"):
             close(grads[k[5:]], TINY[k], 1e-4, 1e-7)
 
