@@ -21,7 +21,7 @@ OPT_SHADOW_F16 = 2                    # OR-ed into the mutate_grad / first_step 
 EPI_NONE, EPI_GELU, EPI_DGELU, EPI_RELU, EPI_DRELU, EPI_GELUG, EPI_MUL = 0, 1, 2, 3, 4, 5, 6
 MT_MAX = 24
 PROF_CLASSES = ("gemm_fwd", "gemm_dgrad", "gemm_wgrad", "lm_head", "attn_fwd", "attn_bwd", "layernorm", "loss", "optimizer", "reduce", "other")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 
@@ -125,6 +125,10 @@ PROTOTYPES = {
     "ctmi_row_lse": (i32, [vp, i64, vp, i64, i64, i32, vp]),
     "ctmi_group_topk": (i32, [vp, i64, vp, vp, f32, vp, vp, i64, i32, i64, i32, i32, vp]),
     "ctmi_scores_filter": (i32, [vp, i64, f32, vp, i64, f32, vp, i64, i64, i64, vp]),
+    "ctmi_lora_project": (i32, [vp, i64, vp, i64, i32, vp, i64, i64, i64, i64, f32, i32, vp]),
+    "ctmi_lora_expand_add": (i32, [vp, i64, vp, i64, i32, vp, i64, i64, i64, i64, i32, vp]),
+    "ctmi_lora_wgrad_ws": (i64, [i64, i64, i64]),
+    "ctmi_lora_wgrad": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i64, f32, vp, i64, i32, vp]),
     "ctmi_probe": (i32, [i32, vp, vp, vp]),
     "ctmi_clock_probe": (i32, [i32, vp, vp]),
     "ctmi_probe_dyn_lds": (i32, [i64, vp, vp]),

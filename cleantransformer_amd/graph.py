@@ -19,7 +19,8 @@ them into a 48-byte device record before each replay (optimizer.py), so schedule
 The first ``warmup`` calls run EAGERLY on their own batches (they are real training steps: lazily created optimizer state, compute-dtype weight
 copies and the grouped weight-gradient work lists all appear there, outside any capture); the next call captures and replays.  A batch of another
 shape, or ``model.eval()``, falls back to an eager step (and re-captures if the new shape persists).  Single-GPU: under DistributedDataParallel the
-step stays eager — its tied-gradient row exchange agrees on a capacity through pinned host memory inside backward.
+step stays eager — its tied-gradient row exchange agrees on a capacity through pinned host memory inside backward.  A model that carries low-rank
+adapters (lora.py) also runs eagerly, with ``fallback_reason`` set.
 """
 from __future__ import annotations
 
@@ -92,6 +93,9 @@ class GraphedStep:
         self.calls += 1
         shape = (tuple(input_ids.shape), input_ids.dtype, attention_mask.dtype, labels.dtype)
         usable = self.enabled and self.model.training and input_ids.is_cuda and torch.is_grad_enabled()
+        if usable and getattr(self.model, "_ct_lora", None) is not None:
+            usable = False                                            # adapters (lora.py): the adapter block path is not captured
+            self.fallback_reason = "low-rank adapters: the step runs eagerly (GraphedStep does not capture the adapter block path)"
         if not usable or self.calls <= self.warmup:
             if self.graph is not None:
                 self._drop()

@@ -236,6 +236,131 @@ class BloomBlockDropoutFn(torch.autograd.Function):
                 None, None, None, None, None, None, None)
 
 
+def _lora_of(linear: torch.nn.Module):
+    """(A [r,in], B [out,r], scaling) of a Linear that cleantransformer_amd.lora.apply_lora gave an adapter, else None."""
+    a = getattr(linear, "lora_A", None)
+    return None if a is None else (a.weight, linear.lora_B.weight, float(linear.lora_scaling))
+
+
+def _lora_fwd(x2: Tensor, y: Tensor, a_c: Tensor, b_c: Tensor, scaling: float) -> Tensor:
+    """y += scaling * (x A^T) B^T in place (y already holds x W^T + bias (+ residual): those epilogues are linear); returns scaling * x A^T."""
+    xa = ops.lora_project(x2, a_c, False, alpha=scaling)
+    ops.lora_expand_add(xa, b_c, y, False)
+    return xa
+
+
+class BloomBlockLoraFn(torch.autograd.Function):
+    """The block with low-rank adapters on any of query_key_value / dense / dense_4h_to_h (cleantransformer_amd/lora.py): the per-op launch sequence of
+    BloomBlockDropoutFn at p = 0, plus project + expand-add (csrc/lora.hip) after the base GEMM of each adapted projection.  The backward computes what
+    ctx.needs_input_grad asks for and nothing else: with the base frozen that is the data-gradient chain, per adapter dxa = scaling * dy B,
+    dB = dy^T xa, dA = dxa^T x and the expand-add of dxa A into the data gradient — no base weight-gradient GEMM, no bias column sum, and no dx for a
+    block whose input needs none.  `adapters` is three (A, B) pairs or (None, None), flattened; `scalings` the three factors."""
+
+    @staticmethod
+    def forward(ctx, x, ln1_w, ln1_b, wqkv, bqkv, wd, bd, ln2_w, ln2_b, w1, b1, w2, b2, aq, bq, ad, bdd, a2, b2l, actx: _AttnCtx, eps: float,
+                post_ln_res: bool, scalings, kv_out: list):
+        B, S, H = x.shape
+        T = B * S
+        nh = actx.nh
+        hd = H // nh
+        cd = x.dtype
+        x2 = x.reshape(T, H)
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        cw = ops.compute_weight
+        s_q, s_d, s_2 = scalings
+        ln1, mean1, rstd1 = ops.layernorm_fwd(x2, ln1_w.detach(), ln1_b.detach(), eps)
+        qkv = ops.linear_fwd(ln1, cw(wqkv, cd), bqkv.detach())
+        xa_q = _lora_fwd(ln1, qkv, cw(aq, cd), cw(bq, cd), s_q) if aq is not None else None
+        desc = ops.fused_qkv_desc(B, S, nh, hd, causal=S > 1)
+        att = torch.empty((T, H), dtype=cd, device=x.device)
+        stat_m, stat_l = ops.attn_fwd(qkv, qkv[:, hd:], qkv[:, 2 * hd:], att, desc, actx.slopes, actx.mask)
+        h1 = ops.linear_fwd(att, cw(wd, cd), bd.detach(), residual=ln1 if post_ln_res else x2)
+        xa_d = _lora_fwd(att, h1, cw(ad, cd), cw(bdd, cd), s_d) if ad is not None else None
+        ln2, mean2, rstd2 = ops.layernorm_fwd(h1, ln2_w.detach(), ln2_b.detach(), eps)
+        u = torch.empty((T, 4 * H), dtype=cd, device=x.device)
+        g = ops.linear_fwd(ln2, cw(w1, cd), b1.detach(), epilogue=_lib.EPI_GELU, aux_out=u)
+        out = ops.linear_fwd(g, cw(w2, cd), b2.detach(), residual=ln2 if post_ln_res else h1)
+        xa_2 = _lora_fwd(g, out, cw(a2, cd), cw(b2l, cd), s_2) if a2 is not None else None
+        ctx.save_for_backward(x2, ln1_w, wqkv, wd, ln2_w, w1, w2, aq, bq, ad, bdd, a2, b2l, xa_q, xa_d, xa_2,
+                              mean1, rstd1, ln1, qkv, att, stat_m, stat_l, h1, mean2, rstd2, ln2, u, g)
+        ctx.actx, ctx.desc, ctx.post_ln_res, ctx.shape, ctx.scalings = actx, desc, post_ln_res, (B, S, H), scalings
+        qv = qkv.view(B, S, nh, 3, hd)
+        kv_out.append((qv[:, :, :, 1, :].transpose(1, 2), qv[:, :, :, 2, :].transpose(1, 2)))
+        return out.view(B, S, H)
+
+    @staticmethod
+    def backward(ctx, dout):
+        if dout is None:
+            return (None,) * 24
+        (x2, ln1_w, wqkv, wd, ln2_w, w1, w2, aq, bq, ad, bdd, a2, b2l, xa_q, xa_d, xa_2,
+         mean1, rstd1, ln1, qkv, att, stat_m, stat_l, h1, mean2, rstd2, ln2, u, g) = ctx.saved_tensors
+        B, S, H = ctx.shape
+        T = B * S
+        hd = H // ctx.actx.nh
+        cd = x2.dtype
+        post = ctx.post_ln_res
+        need = ctx.needs_input_grad
+        s_q, s_d, s_2 = ctx.scalings
+        cw = ops.compute_weight
+        grads = [None] * 24
+        dout2 = dout.reshape(T, H)
+        dout2 = dout2 if dout2.is_contiguous() else dout2.contiguous()
+
+        def adapter(dy, xa, x_in, a, b, scaling, ia, ib):
+            """dxa = scaling * dy B (always: the data gradient needs it); dB = dy^T xa and dA = dxa^T x when asked for (xa carries the scaling)"""
+            dxa = ops.lora_project(dy, cw(b, cd), True, alpha=scaling)
+            if need[ib]:
+                grads[ib] = ops.lora_wgrad(dy, xa)
+            if need[ia]:
+                grads[ia] = ops.lora_wgrad(dxa, x_in)
+            return dxa
+
+        # MLP: out = res2 + W2 gelu(W1 ln2 + b1) + b2 (+ adapter on the 4h -> h projection)
+        if need[11]:
+            grads[11] = ops.linear_wgrad(dout2, g)
+        if need[12]:
+            grads[12] = ops.colsum(dout2)
+        du = ops.linear_dgrad(dout2, cw(w2, cd), epilogue=_lib.EPI_DGELU, aux_in=u)
+        if a2 is not None:
+            dxa = adapter(dout2, xa_2, g, a2, b2l, s_2, 17, 18)
+            # du += (dxa A2) * gelu'(u): the activation derivative multiplies the adapter's share of dg too, so it goes through the GEMM that has the
+            # dGELU epilogue (K = r), accumulating into du
+            a_c = cw(a2, cd)
+            ops.gemm(dxa, dxa.stride(0), False, a_c, a_c.stride(0), True, T, 4 * H, dxa.shape[1], out=du, epilogue=_lib.EPI_DGELU, aux_in=u, beta=1)
+        if need[9]:
+            grads[9] = ops.linear_wgrad(du, ln2)
+        if need[10]:
+            grads[10] = ops.colsum(du)
+        dln2 = ops.linear_dgrad(du, cw(w1, cd), residual=dout2 if post else None)
+        dh1, dln2_w, dln2_b = ops.layernorm_bwd(dln2, h1, ln2_w.detach(), mean2, rstd2, dres=None if post else dout2)
+        grads[7], grads[8] = (dln2_w if need[7] else None), (dln2_b if need[8] else None)
+        # attention: h1 = res1 + Wd att + bd (+ adapter)
+        if need[5]:
+            grads[5] = ops.linear_wgrad(dh1, att)
+        if need[6]:
+            grads[6] = ops.colsum(dh1)
+        datt = ops.linear_dgrad(dh1, cw(wd, cd))
+        if ad is not None:
+            dxa = adapter(dh1, xa_d, att, ad, bdd, s_d, 15, 16)
+            ops.lora_expand_add(dxa, cw(ad, cd), datt, True)
+        dqkv = torch.empty_like(qkv)
+        ops.attn_bwd(qkv, qkv[:, hd:], qkv[:, 2 * hd:], att, datt, stat_m, stat_l, dqkv, dqkv[:, hd:], dqkv[:, 2 * hd:], ctx.desc,
+                     ctx.actx.slopes, ctx.actx.mask)
+        if need[3]:
+            grads[3] = ops.linear_wgrad(dqkv, ln1)
+        if need[4]:
+            grads[4] = ops.colsum(dqkv)
+        dxa = adapter(dqkv, xa_q, ln1, aq, bq, s_q, 13, 14) if aq is not None else None
+        if need[0] or need[1] or need[2]:
+            dln1 = ops.linear_dgrad(dqkv, cw(wqkv, cd), residual=dh1 if post else None)
+            if dxa is not None:
+                ops.lora_expand_add(dxa, cw(aq, cd), dln1, True)
+            dx, dln1_w, dln1_b = ops.layernorm_bwd(dln1, x2, ln1_w.detach(), mean1, rstd1, dres=None if post else dh1)
+            grads[0] = dx.view(B, S, H) if need[0] else None
+            grads[1], grads[2] = (dln1_w if need[1] else None), (dln1_b if need[2] else None)
+        return tuple(grads)
+
+
 def _decode_block(blk: "BloomBlock", x: Tensor, actx: _AttnCtx, past, eps: float, post_ln_res: bool):
     """Inference-only block forward with a KV cache (modeling_bloom.py:88-92): same kernels, nothing saved."""
     B, S, H = x.shape
@@ -248,6 +373,9 @@ def _decode_block(blk: "BloomBlock", x: Tensor, actx: _AttnCtx, past, eps: float
     x2 = x2 if x2.is_contiguous() else x2.contiguous()
     ln1, _, _ = ops.layernorm_fwd(x2, blk.input_layernorm.weight.detach(), blk.input_layernorm.bias.detach(), eps)
     qkv = ops.linear_fwd(ln1, ops.compute_weight(sa.query_key_value.weight, cd), sa.query_key_value.bias.detach())
+    lq, ld, l2 = _lora_of(sa.query_key_value), _lora_of(sa.dense), _lora_of(mlp.dense_4h_to_h)
+    if lq is not None:
+        _lora_fwd(ln1, qkv, ops.compute_weight(lq[0], cd), ops.compute_weight(lq[1], cd), lq[2])
     qv = qkv.view(B, S, nh, 3, hd)
     k_new, v_new = qv[:, :, :, 1, :].transpose(1, 2), qv[:, :, :, 2, :].transpose(1, 2)
     k = torch.cat((past[0], k_new), dim=-2).contiguous()                                   # [B,nh,Sk,hd]
@@ -259,12 +387,16 @@ def _decode_block(blk: "BloomBlock", x: Tensor, actx: _AttnCtx, past, eps: float
     att = torch.empty((T, H), dtype=cd, device=x.device)
     ops.attn_fwd(qkv, k, v, att, desc, actx.slopes, actx.mask)
     h1 = ops.linear_fwd(att, ops.compute_weight(sa.dense.weight, cd), sa.dense.bias.detach(), residual=ln1 if post_ln_res else x2)
+    if ld is not None:
+        _lora_fwd(att, h1, ops.compute_weight(ld[0], cd), ops.compute_weight(ld[1], cd), ld[2])
     ln2, _, _ = ops.layernorm_fwd(h1, blk.post_attention_layernorm.weight.detach(), blk.post_attention_layernorm.bias.detach(), eps)
     u = torch.empty((T, 4 * H), dtype=cd, device=x.device)
     g = ops.linear_fwd(ln2, ops.compute_weight(mlp.dense_h_to_4h.weight, cd), mlp.dense_h_to_4h.bias.detach(),
                        epilogue=_lib.EPI_GELU, aux_out=u)
     out = ops.linear_fwd(g, ops.compute_weight(mlp.dense_4h_to_h.weight, cd), mlp.dense_4h_to_h.bias.detach(),
                          residual=ln2 if post_ln_res else h1)
+    if l2 is not None:
+        _lora_fwd(g, out, ops.compute_weight(l2[0], cd), ops.compute_weight(l2[1], cd), l2[2])
     return out.view(B, S, H), (k, v)
 
 
@@ -304,6 +436,8 @@ class EmbedFn(torch.autograd.Function):
     def backward(ctx, dout: Tensor):
         (ids,) = ctx.saved_tensors
         tie = ctx.tie
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None                  # frozen table: no scatter
         dout = dout if dout.is_contiguous() else dout.contiguous()
         if tie is not None and tie.pending is not None:
             dw, tie.pending = tie.pending, None
@@ -351,13 +485,14 @@ class LMHeadFn(torch.autograd.Function):
         sync = getattr(weight, "_ct_tied_sync", None) if tied else None       # set by trainer/ddp.py on the shared [V,H] parameter
         pre = sync.prescale(weight) if sync is not None else None             # 1/world when this step reduces the dense part early
         Vp = ops.ZERO_PADDED.pop(d2.data_ptr(), (None, None))[0] if d2.is_cuda else None
+        want_dw = ctx.needs_input_grad[1]                  # a frozen table gets no [V,H] weight-gradient GEMM
         wpad = getattr(weight, "_ct_shadow_pad", None)
         if Vp is not None and d2.stride() == (Vp, 1) and wpad is not None and wpad.shape[0] == Vp and wpad.dtype == h2.dtype:
             # zero-padded dlogits [T, Vp] against the zero-padded table copy [Vp, H]: both GEMMs see aligned, 32-divisible
             # extents (K = Vp for the dgrad, M = Vp for the wgrad) and the padding contributes exact zeros
             dp = d2.as_strided((B * S, Vp), (Vp, 1))
             dh = ops.linear_dgrad(dp, wpad)
-            dw = ops.linear_wgrad(dp, h2, alpha=1.0 if pre is None else pre)[:V]
+            dw = ops.linear_wgrad(dp, h2, alpha=1.0 if pre is None else pre)[:V] if want_dw else None
         else:
             d2 = d2 if d2.is_contiguous() else d2.contiguous()
             rows = sync.chunk_rows(V, H) if pre is not None else V
@@ -374,7 +509,7 @@ class LMHeadFn(torch.autograd.Function):
                 dh = ops.linear_dgrad(d2, wc)
                 return dh.view(B, S, H), None, None
             dh = ops.linear_dgrad(d2, wc)
-            dw = ops.linear_wgrad(d2, h2, alpha=1.0 if pre is None else pre)
+            dw = ops.linear_wgrad(d2, h2, alpha=1.0 if pre is None else pre) if want_dw else None
         if tied:
             tie.pending = dw                                   # the embedding backward (always later) finishes and returns it
             if pre is not None:
@@ -526,6 +661,20 @@ class BloomBlock(torch.nn.Module):
             return _decode_block(self, hidden_states, actx, k_v_past, self.eps, self.apply_residual_connection_post_layernorm)
         p_hidden = float(self.hidden_dropout) if self.training else 0.0
         p_attn = float(self.self_attention.attention_dropout.p) if self.training else 0.0
+        lora = (_lora_of(sa.query_key_value), _lora_of(sa.dense), _lora_of(mlp.dense_4h_to_h))
+        if any(l is not None for l in lora):
+            if p_hidden > 0.0 or p_attn > 0.0:
+                raise NotImplementedError("dropout > 0 together with low-rank adapters is not implemented (hidden_dropout / attention_dropout must be 0)")
+            flat = [t for l in lora for t in ((None, None) if l is None else l[:2])]
+            kv = []
+            out = BloomBlockLoraFn.apply(
+                hidden_states, self.input_layernorm.weight, self.input_layernorm.bias,
+                sa.query_key_value.weight, sa.query_key_value.bias, sa.dense.weight, sa.dense.bias,
+                self.post_attention_layernorm.weight, self.post_attention_layernorm.bias,
+                mlp.dense_h_to_4h.weight, mlp.dense_h_to_4h.bias, mlp.dense_4h_to_h.weight, mlp.dense_4h_to_h.bias,
+                *flat, actx, self.eps, self.apply_residual_connection_post_layernorm,
+                tuple(1.0 if l is None else l[2] for l in lora), kv)
+            return out, kv[0]
         if p_hidden > 0.0 or p_attn > 0.0:
             from .. import rng
             kv = []

@@ -1158,3 +1158,63 @@ def compute_weight(p: Tensor, dtype: torch.dtype) -> Tensor:
         p._ct_shadow_ver = p._version
         p._ct_shadow_ptr = p.data_ptr()
     return sh
+
+
+# ------------------------------------------------------------------------------------------------ low-rank adapters (csrc/lora.hip)
+def _row_major(t: Tensor) -> Tensor:
+    return t if (t.dim() == 2 and t.stride(1) == 1) else t.contiguous()
+
+
+def lora_project(x: Tensor, w: Tensor, w_kmajor: bool = False, alpha: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
+    """out[T,r] = alpha * x[T,K] @ w^T with w [r,K] (w_kmajor=False: x A^T) or w [K,r] (w_kmajor=True: dy B); storage dtype of x.
+    bf16 / fp16: ctmi_lora_project; fp32: the same product through ctmi_gemm."""
+    _need_cuda(x, w)
+    x, w = _row_major(x), _row_major(w)
+    T, K = x.shape
+    r = w.shape[1] if w_kmajor else w.shape[0]
+    if (w.shape[0] if w_kmajor else w.shape[1]) != K or w.dtype != x.dtype:
+        raise _lib.CtmiError(f"lora_project: x {tuple(x.shape)} {x.dtype} against w {tuple(w.shape)} {w.dtype} (k-major: {w_kmajor})")
+    if out is None:
+        out = torch.empty((T, r), dtype=x.dtype, device=x.device)
+    if x.dtype == torch.float32:
+        return gemm(x, x.stride(0), False, w, w.stride(0), bool(w_kmajor), T, r, K, out=out, alpha=alpha)
+    check(_lib.load().ctmi_lora_project(_p(x), x.stride(0), _p(w), w.stride(0), int(w_kmajor), _p(out), out.stride(0), T, K, r, float(alpha),
+                                        dt_code(x.dtype), _stream()), "lora_project")
+    return out
+
+
+def lora_expand_add(xa: Tensor, w: Tensor, y: Tensor, w_kmajor: bool = False) -> Tensor:
+    """y[T,N] += xa[T,r] @ w in place, with w [N,r] (w_kmajor=False: xa B^T) or w [r,N] (w_kmajor=True: dxa A).  y may be a column window of a wider
+    buffer (its row stride is the leading dimension)."""
+    _need_cuda(xa, w, y)
+    xa, w = _row_major(xa), _row_major(w)
+    T, r = xa.shape
+    N = w.shape[1] if w_kmajor else w.shape[0]
+    if (w.shape[0] if w_kmajor else w.shape[1]) != r or tuple(y.shape) != (T, N) or y.stride(1) != 1 or not (w.dtype == xa.dtype == y.dtype):
+        raise _lib.CtmiError(f"lora_expand_add: xa {tuple(xa.shape)} w {tuple(w.shape)} y {tuple(y.shape)} (k-major: {w_kmajor})")
+    if xa.dtype == torch.float32:
+        gemm(xa, xa.stride(0), False, w, w.stride(0), bool(w_kmajor), T, N, r, out=y, beta=1)
+        return y
+    check(_lib.load().ctmi_lora_expand_add(_p(xa), xa.stride(0), _p(w), w.stride(0), int(w_kmajor), _p(y), y.stride(0), T, N, r,
+                                           dt_code(xa.dtype), _stream()), "lora_expand_add")
+    return y
+
+
+def lora_wgrad(l: Tensor, r: Tensor, alpha: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
+    """out[P,Q] (fp32) = alpha * l[T,P]^T @ r[T,Q], min(P,Q) <= 64: dB = scaling * dy^T xa, dA = dxa^T x.  The T reduction is split into slabs
+    that are added in a fixed order: bit-identical from run to run."""
+    _need_cuda(l, r)
+    l, r = _row_major(l), _row_major(r)
+    T, P = l.shape
+    Q = r.shape[1]
+    if r.shape[0] != T or l.dtype != r.dtype:
+        raise _lib.CtmiError(f"lora_wgrad: l {tuple(l.shape)} {l.dtype} against r {tuple(r.shape)} {r.dtype}")
+    if out is None:
+        out = torch.empty((P, Q), dtype=torch.float32, device=l.device)
+    if l.dtype == torch.float32:
+        return gemm(l, l.stride(0), True, r, r.stride(0), True, P, Q, T, out=out, out_f32=True, alpha=alpha)
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.ctmi_lora_wgrad_ws(T, P, Q)), dtype=torch.float32, device=l.device)
+    check(lib.ctmi_lora_wgrad(_p(l), l.stride(0), _p(r), r.stride(0), _p(out), out.stride(0), T, P, Q, float(alpha), _p(ws), ws.numel() * 4,
+                              dt_code(l.dtype), _stream()), "lora_wgrad")
+    return out

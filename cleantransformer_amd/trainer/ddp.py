@@ -287,6 +287,9 @@ class DistributedDataParallel(torch.nn.Module):
                  process_group=None, bucket_cap_mb=None, find_unused_parameters=False, check_reduction=False,
                  gradient_as_bucket_view=False, static_graph=False, comm_dtype=None, **kwargs):
         super().__init__()
+        if getattr(module, "_ct_lora", None) is not None:
+            raise NotImplementedError("DistributedDataParallel around a model with low-rank adapters (cleantransformer_amd.lora) is not implemented: "
+                                      "merge_lora() first, or train the adapters on one GPU")
         # comm_dtype=torch.bfloat16 (or CTMI_DDP_COMM_DTYPE=bf16): buckets travel as bf16 — half the xGMI bytes of the fp32
         # default — and are widened back into the fp32 bucket the gradients view ("O2"-style bf16 gradient communication,
         # SURVEY §8(f)2).  Opt-in: the averaged gradients then carry bf16 rounding (~2^-9 relative), outside the 1e-4 parity

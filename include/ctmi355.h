@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define CTMI_ABI_VERSION 15
+#define CTMI_ABI_VERSION 16
 
 enum ctmi_dtype { CTMI_F32 = 0, CTMI_BF16 = 1, CTMI_F16 = 2 };
 /* CTMI_F16 (ABI v14): IEEE half storage with fp32 accumulation and statistics — torch.autocast(dtype=float16) of examples/ft_bloom_DDP.py:107-128.
@@ -390,6 +390,24 @@ int64_t ctmi_bloom_block_bwd_ws(int64_t B, int64_t S, int64_t H, int64_t nh, int
  * launches that gain from a side stream. */
 int ctmi_bloom_block_wgrad_grouped(int64_t B, int64_t S, int64_t H, int dtype, int flags);
 int ctmi_bloom_block_bwd(const ctmi_bloom_block* blk /* host */, const ctmi_bloom_block_grads* gr /* host */, void* stream);
+
+/* ---- low-rank adapters (ABI v16; csrc/lora.hip).  y = x W^T + b + scaling * (x A^T) B^T with A [r, in], B [out, r] (the peft parametrisation; the
+ * reference trainer imports peft, CleanTransformer/trainer/trainer.py) next to the frozen Linears of modeling_bloom.py:79,121,267.  Three products
+ * whose small dimension is r, on v_mfma_f32_16x16x32 with fp32 accumulation.  dtype = CTMI_BF16 or CTMI_F16 (fp32 callers use ctmi_gemm); any T >= 1;
+ * K, N, P, Q, r and all leading dimensions multiples of 8; 8 <= r <= 64; 16-byte aligned x / w / y / l / r.  Anything else returns
+ * CTMI_ERR_UNSUPPORTED before any launch.  Nothing outside the stated extents is read or written.
+ *   project:     out[T, r] (storage dtype, ldo) = alpha * x[T, K] w^T      w_kmajor = 0: w is [r, K] (x A^T);  1: w is [K, r] (dy B)
+ *   expand-add:  y[T, N] (ldy >= N, in place)  += xa[T, r] w               w_kmajor = 0: w is [N, r] (xa B^T); 1: w is [r, N] (dxa A)
+ *   wgrad:       out[P, Q] (fp32, ldo)          = alpha * l[T, P]^T r[T, Q]   min(P, Q) <= 64
+ *                T is cut into slabs whose partial products go to ws (ctmi_lora_wgrad_ws(T, P, Q) floats) and are added in slab order by a second
+ *                launch: no floating-point atomics, bit-identical from run to run. */
+int ctmi_lora_project(const void* x, int64_t ldx, const void* w, int64_t ldw, int w_kmajor, void* out, int64_t ldo,
+                      int64_t T, int64_t K, int64_t r, float alpha, int dtype, void* stream);
+int ctmi_lora_expand_add(const void* xa, int64_t ldxa, const void* w, int64_t ldw, int w_kmajor, void* y, int64_t ldy,
+                         int64_t T, int64_t N, int64_t r, int dtype, void* stream);
+int64_t ctmi_lora_wgrad_ws(int64_t T, int64_t P, int64_t Q);
+int ctmi_lora_wgrad(const void* l, int64_t ldl, const void* r, int64_t ldr, float* out, int64_t ldo, int64_t T, int64_t P, int64_t Q,
+                    float alpha, float* ws, int64_t ws_bytes, int dtype, void* stream);
 
 /* ---- hardware probe (diagnostics: dumps MFMA / LDS-transpose lane layouts into out[]; used by tests only) */
 int ctmi_probe(int which, const float* in /* device */, float* out /* device, 256 floats */, void* stream);
