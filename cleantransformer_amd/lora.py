@@ -4,8 +4,9 @@
 
 next to the frozen ``query_key_value`` / ``dense`` / ``dense_4h_to_h`` Linears of every block, with peft's parameter names
 (``<linear>.lora_A.weight``, ``<linear>.lora_B.weight``).  The adapters are fp32 master parameters like every other parameter of the package; the
-products run on the three kernel families of csrc/lora.hip (project, expand-add, skinny weight gradient) from ``models.modeling_bloom.BloomBlockLoraFn``,
-whose backward launches nothing for a frozen parameter.
+products run on the three kernel families of csrc/lora.hip (project, expand-add, skinny weight gradient) from the per-op block of ``models.modeling_bloom``
+(``BloomBlockOpsFn``: one forward and one backward routine shared with the dropout path; KV-cache decode calls the same forward routine), whose backward
+launches nothing for a frozen parameter.
 
     model = apply_lora(model, LoraConfig(r=16, lora_alpha=32))
     optimizer = AdamW(model.parameters(), ...)          # parameters without a gradient are skipped

@@ -158,11 +158,8 @@ class GPT2BlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo, mask: ops.MaskInfo, nh: int, eps: float, scale: float, kv_out: list):
         B, S, H = x.shape
-        cd = x.dtype
-        x2 = x.reshape(B * S, H)
-        x2 = x2 if x2.is_contiguous() else x2.contiguous()
-        params = (n1w.detach(), n1b.detach(), ops.compute_weight(wa, cd), ba.detach(), ops.compute_weight(wp, cd), bp.detach(),
-                  n2w.detach(), n2b.detach(), ops.compute_weight(wf, cd), bf.detach(), ops.compute_weight(wo, cd), bo.detach())
+        x2 = ops._c(x.reshape(B * S, H))
+        params = ops.block_params((n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo), x.dtype)
         acts = ops.bloom_block_fwd(x2, params, mask, None, eps, False, B, S, nh, flags=_lib.BLK_QKV_BLOCKED | _lib.BLK_WGRAD_IN_OUT | _lib.BLK_W_IN_OUT,
                                    attn_scale=scale, future_fill=-1e4)
         ops.note_block_params(mask, (n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo))
@@ -182,11 +179,8 @@ class GPT2BlockFn(torch.autograd.Function):
             return (None,) * 18
         x2, n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo, slab = ctx.saved_tensors
         B, S, H = ctx.shape
-        cd = x2.dtype
-        dout2 = dout.reshape(B * S, H)
-        dout2 = dout2 if dout2.is_contiguous() else dout2.contiguous()
-        params = (n1w.detach(), n1b.detach(), ops.compute_weight(wa, cd), ba.detach(), ops.compute_weight(wp, cd), bp.detach(),
-                  n2w.detach(), n2b.detach(), ops.compute_weight(wf, cd), bf.detach(), ops.compute_weight(wo, cd), bo.detach())
+        dout2 = ops._c(dout.reshape(B * S, H))
+        params = ops.block_params((n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo), x2.dtype)
         ctx.kv.release()
         defer = x2.is_cuda and ops.params_allow_deferred_grads((n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo), ctx.mask)
         dx, g = ops.bloom_block_bwd(ops.BlockActs.rebuild(slab, ctx.geo), x2, params, ctx.mask, None, ctx.eps, False, dout2, defer_join=defer)

@@ -613,6 +613,15 @@ class BlockActs:
         return a
 
 
+def kv_views(qkv: Tensor, B: int, S: int, nh: int, blocked: bool):
+    """The K and V parts of a fused QKV activation [B*S, 3H] as [B,nh,S,hd] views (no copy)."""
+    if blocked:                                                         # q | k | v  [B,S,3,nh,hd]  (GPT-2's c_attn)
+        qv = qkv.view(B, S, 3, nh, -1)
+        return qv[:, :, 1].transpose(1, 2), qv[:, :, 2].transpose(1, 2)
+    qv = qkv.view(B, S, nh, 3, -1)                                      # head-interleaved [B,S,nh,3,hd]  (Bloom's query_key_value)
+    return qv[:, :, :, 1, :].transpose(1, 2), qv[:, :, :, 2, :].transpose(1, 2)
+
+
 class KVOut(list):
     """The out-parameter through which a block node hands back its presents; it also carries the caller's grad mode into the node's
     forward (inside autograd.Function.forward grad mode is always off, and needs_input_grad ignores torch.no_grad())."""
@@ -638,12 +647,7 @@ class LazyKV:
             self._kv = (k.contiguous(), v.contiguous())
 
     def _views(self, acts: BlockActs):
-        B, S, nh = acts.B, acts.S, acts.nh
-        if self._blocked:                                               # q | k | v  [B,S,3,nh,hd]
-            qv = acts.qkv.view(B, S, 3, nh, -1)
-            return qv[:, :, 1].transpose(1, 2), qv[:, :, 2].transpose(1, 2)
-        qv = acts.qkv.view(B, S, nh, 3, -1)                             # head-interleaved [B,S,nh,3,hd]
-        return qv[:, :, :, 1, :].transpose(1, 2), qv[:, :, :, 2, :].transpose(1, 2)
+        return kv_views(acts.qkv, acts.B, acts.S, acts.nh, self._blocked)
 
     def release(self) -> None:
         """Called by the block's backward: the activations are about to be freed (views already handed out keep their storage)."""
@@ -1158,6 +1162,11 @@ def compute_weight(p: Tensor, dtype: torch.dtype) -> Tensor:
         p._ct_shadow_ver = p._version
         p._ct_shadow_ptr = p.data_ptr()
     return sh
+
+
+def block_params(ps, dtype: torch.dtype):
+    """The 12 parameters of a block (_lib.BLK_PARAMS order) as the kernels take them: detached, the four matrices in the compute dtype."""
+    return tuple(compute_weight(p, dtype) if p.dim() == 2 else p.detach() for p in ps)
 
 
 # ------------------------------------------------------------------------------------------------ low-rank adapters (csrc/lora.hip)
