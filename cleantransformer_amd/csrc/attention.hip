@@ -944,7 +944,7 @@ static int fill_params(AttnP& p, const ctmi_attn_desc* d, int dtype, const char*
     p.drop_scale = 1.0f / (1.0f - d->dropout_p);
     p.future_fill = d->future_fill == 0.0f ? FINFO_MIN : d->future_fill;
     CTMI_REQUIRE(p.future_fill < 0.0f && p.future_fill >= FINFO_MIN, "%s: future_fill must be 0 (= finfo.min) or a negative finite value", who);
-    { static int dbg = -1; if (dbg < 0) { const char* e = getenv("CTMI_ATTN_DBG"); dbg = e ? atoi(e) : 0; } p.dbg = dbg; }
+    { static const int dbg = ctmi_env_int("CTMI_ATTN_DBG", 0); p.dbg = dbg; }
     const int vec = dtype == CTMI_F32 ? 4 : 8;
     auto ok = [&](const void* ptr, int64_t a, int64_t b2, int64_t c) {
         return ptr == nullptr || (((((uintptr_t)ptr) & 15) == 0) && a % vec == 0 && b2 % vec == 0 && c % vec == 0);

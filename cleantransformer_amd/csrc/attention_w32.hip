@@ -852,7 +852,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && (HD == 64 || MODE != 0)) ? 2 :
 std::atomic<int> g_w32_mask{-1};
 int w32_mask() {
     int v = g_w32_mask.load(std::memory_order_relaxed);
-    if (v < 0) { const char* e = getenv("CTMI_ATTN_W32"); v = e ? (atoi(e) & 3) : 3; g_w32_mask.store(v, std::memory_order_relaxed); }
+    if (v < 0) { v = ctmi_env_int("CTMI_ATTN_W32", 3) & 3; g_w32_mask.store(v, std::memory_order_relaxed); }
     return v;
 }
 bool w32_ok(const AttnP& p) {

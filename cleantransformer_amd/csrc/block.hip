@@ -21,9 +21,6 @@
 //   dx   = LN1'(dln1) + dh1    [+ partial rows of dln1_w, dln1_b]
 //   join;  ONE reduce launch turns all partial rows into the 8 small gradient vectors.
 #include "common.h"
-#ifndef CTMI_BLOCK_TAIL
-#define CTMI_BLOCK_TAIL 1      // 0: the sum of the K-halves right behind the grouped launch (round 5), for A/B builds
-#endif
 #include <math.h>
 #include <stdlib.h>
 #include <mutex>
@@ -122,8 +119,6 @@ int linear_dgrad(const void* dy, const void* w, void* dx, int64_t T, int64_t Nou
 // dW[Nout,Kin] (fp32) = dy[T,Nout]^T x[T,Kin]   — or, in_out: dW[Kin,Nout] = x^T dy (a Conv1D weight is stored [in,out])
 int linear_wgrad(const void* dy, const void* x, float* dw, int64_t T, int64_t Nout, int64_t Kin, int dtype, void* ws, int64_t ws_bytes,
                  hipStream_t st, bool in_out = false) {
-    { static int dbg = -1; if (dbg < 0) { const char* e = getenv("CTMI_BLOCK_DBG"); dbg = e ? atoi(e) : 0; }
-      if (dbg & 1) return CTMI_OK; }                                    // timing experiments only: 1 = skip the layer weight-gradient GEMMs
     if (in_out)
         return ctmi_gemm(x, Kin, 1, dy, Nout, 1, dw, Nout, Kin, Nout, T, 1.0f, 0, nullptr, nullptr, CTMI_EPI_NONE, nullptr, nullptr, 1, dtype,
                          ws, ws_bytes, st);
@@ -207,7 +202,6 @@ int64_t bwd_layout(int64_t B, int64_t S, int64_t H, int64_t nh, int dtype, int64
 // stream: the grouped launch fills the 256 CUs by itself — profiles/r05_wgrad_grouped.txt — and callers keep side_stream NULL.)
 extern "C" int ctmi_bloom_block_wgrad_grouped(int64_t B, int64_t S, int64_t H, int dtype, int flags) {
     if (B <= 0 || S <= 0 || H <= 0) return 0;
-    { const char* e = getenv("CTMI_BLOCK_DBG"); if (e && (atoi(e) & 1)) return 0; }
     const int io = (flags & CTMI_BLK_WGRAD_IN_OUT) ? 1 : 0;
     void* const al = reinterpret_cast<void*>(uintptr_t(256));                          // stands for any 16-byte aligned pointer
     float* const fa = reinterpret_cast<float*>(al);
@@ -268,44 +262,66 @@ extern "C" int ctmi_bloom_block_bwd(const ctmi_bloom_block* b, const ctmi_bloom_
     };
 
     const void* dout = gr->dout;
-    static int blk_dbg = -1;
-    if (blk_dbg < 0) { const char* e = getenv("CTMI_BLOCK_DBG"); blk_dbg = e ? atoi(e) : 0; }
-    // the four weight gradients as one grouped launch?  (list order = split order: the tiles of the last partial round — dwd, dwqkv at
-    // Bloom-560M — are the ones cut in two along T)
+    // the four weight gradients, in the order their operands appear.  As one grouped launch?  (list order = split order: the tiles of the last
+    // partial round — dwd, dwqkv at Bloom-560M — are the ones cut in two along T)
     ctmi_wgrad_problem wp[4] = {
         {dout, s.at(CTMI_BLK_G), gr->dw2, nullptr, H, 4 * H, wio ? 1 : 0, 0},
         {W(W_DU), s.at(CTMI_BLK_LN2), gr->dw1, gr->db1, 4 * H, H, wio ? 1 : 0, 0},        // (round 6: the column sums of du / dqkv ride in the grouped launch for [in,out] weights too — there as sums of its B operand)
         {W(W_DH1), s.at(CTMI_BLK_ATT), gr->dwd, nullptr, H, H, wio ? 1 : 0, 0},
         {W(W_DQKV), s.at(CTMI_BLK_LN1), gr->dwqkv, gr->dbqkv, 3 * H, H, wio ? 1 : 0, 0},
     };
-    const bool grouped = !(blk_dbg & 1) && ctmi_wgrad_grouped_ok(wp, 4, T, dt);
+    const int wp_cs[4] = {-1, W_CS_DU, -1, W_CS_DQKV};                  // workspace slot of a product's column sums in the per-product form
+    const bool grouped = ctmi_wgrad_grouped_ok(wp, 4, T, dt);
+    int np2 = 0, ns2 = 2;                                                // partial rows of the LayerNorm-2 backward
+    // bias gradients of the two [T,H]-output Linears: column sums of dout (4h->h) and of dh1 (dense); with ns2 == 4 the LayerNorm-2 backward
+    // has already left them among its partial rows
+    auto out_bias_jobs = [&]() -> int {
+        if (ns2 == 4 && !post) job(WF(W_LNP2) + 2 * H, ns2 * H, np2, gr->db2, H);
+        else RC(colsum_job(dout, H, W_CS_DOUT, gr->db2));
+        if (ns2 == 4) job(WF(W_LNP2) + 3 * H, ns2 * H, np2, gr->dbd, H);
+        else RC(colsum_job(W(W_DH1), H, W_CS_DH1, gr->dbd));
+        return CTMI_OK;
+    };
+    // called where the operands of product i have just been produced.  Per-product form: the parameter stream picks up there and takes the
+    // product and the column sums of its dy (dh1 also brings the two [T,H] bias gradients).  Grouped form: nothing — one launch, below
+    auto wgrad = [&](int i) -> int {
+        if (grouped) return CTMI_OK;
+        RC(fork());
+        if (i == 2) RC(out_bias_jobs());
+        const ctmi_wgrad_problem& p = wp[i];
+        RC(linear_wgrad(p.dy, p.x, p.dw, T, p.n_out, p.n_in, dt, pws, pws_bytes, pst, wio));
+        if (p.db) RC(colsum_job(p.dy, p.n_out, wp_cs[i], p.db));
+        return CTMI_OK;
+    };
     // The launches run inside a lambda so that a failure half-way still reaches the join below: the side stream may already hold
     // work that reads the caller's buffers, and the caller (who frees them on error) only orders against the main stream.
     const int rc_launch = [&]() -> int {
-    if (grouped) {
-        RC(linear_dgrad(dout, b->w2, W(W_DU), T, H, 4 * H, CTMI_BLOCK_GELUG ? CTMI_EPI_MUL : CTMI_EPI_DGELU, s.at(CTMI_BLK_U), nullptr, dt, nullptr, 0, main_st, w_io));
+        // ---- MLP: out = res2 + W2 gelu(W1 ln2 + b1) + b2
+        RC(wgrad(0));
+        RC(linear_dgrad(dout, b->w2, W(W_DU), T, H, 4 * H, CTMI_BLOCK_GELUG ? CTMI_EPI_MUL : CTMI_EPI_DGELU, s.at(CTMI_BLK_U), nullptr, dt, nullptr, 0, main_st, w_io));        // modeling_bloom.py:348-363 fused
+        RC(wgrad(1));
         RC(linear_dgrad(W(W_DU), b->w1, W(W_DLN2), T, 4 * H, H, CTMI_EPI_NONE, nullptr, post ? dout : nullptr, dt, gr->splitk_ws, gr->splitk_ws_bytes, main_st, w_io));
-        int np2 = 0, ns2 = 2;
         RC(ctmi_ln_bwd_parts_internal(W(W_DLN2), s.at(CTMI_BLK_H1), b->ln2_w, s.at<float>(CTMI_BLK_MEAN2), s.at<float>(CTMI_BLK_RSTD2),
                                       post ? nullptr : dout, W(W_DH1), WF(W_LNP2), T, H, dt, 1, &np2, &ns2, main_st));
         job(WF(W_LNP2), ns2 * H, np2, gr->dln2_w, H);
         job(WF(W_LNP2) + H, ns2 * H, np2, gr->dln2_b, H);
+        // ---- attention: h1 = res1 + Wd att + bd
+        RC(wgrad(2));
         RC(linear_dgrad(W(W_DH1), b->wd, W(W_DATT), T, H, H, CTMI_EPI_NONE, nullptr, nullptr, dt, gr->splitk_ws, gr->splitk_ws_bytes, main_st, w_io));
         const ctmi_attn_desc d = fused_qkv_desc(b);
         char* qkv = s.at<char>(CTMI_BLK_QKV);
         char* dqkv = reinterpret_cast<char*>(W(W_DQKV));
         RC(ctmi_attn_bwd(qkv, qkv + qkv_part(b, 1) * e, qkv + qkv_part(b, 2) * e, s.at(CTMI_BLK_ATT), W(W_DATT), s.at<float>(CTMI_BLK_STAT_M), s.at<float>(CTMI_BLK_STAT_L),
                          dqkv, dqkv + qkv_part(b, 1) * e, dqkv + qkv_part(b, 2) * e, WF(W_DELTA), b->slopes, b->kpos, b->kvalid, b->first_valid, nullptr, &d, dt, main_st));
-        // every operand of the four weight gradients exists now
-        RC(fork());
-        if (ns2 == 4 && !post) job(WF(W_LNP2) + 2 * H, ns2 * H, np2, gr->db2, H);
-        else RC(colsum_job(dout, H, W_CS_DOUT, gr->db2));
-        if (ns2 == 4) job(WF(W_LNP2) + 3 * H, ns2 * H, np2, gr->dbd, H);
-        else RC(colsum_job(W(W_DH1), H, W_CS_DH1, gr->dbd));
-        // one stream (the default of the grouped path): the sum of the K-halves waits for the block's last launch and shares it with the
-        // partial-row reductions (ctmi_wgrad_tail below) — the data gradient in between then gets no split-K workspace: the slabs of the halves live there
-        const bool tail = !two && CTMI_BLOCK_TAIL;
-        RC(ctmi_wgrad_grouped_ex(wp, 4, T, dt, pws, pws_bytes, pst, tail));
+        RC(wgrad(3));
+        if (grouped) {
+            // every operand of the four weight gradients exists now
+            RC(fork());
+            RC(out_bias_jobs());
+            // one stream (the default of the grouped path): the sum of the K-halves waits for the block's last launch and shares it with the
+            // partial-row reductions (ctmi_wgrad_tail below) — the data gradient in between then gets no split-K workspace: the slabs of the halves live there
+            RC(ctmi_wgrad_grouped_ex(wp, 4, T, dt, pws, pws_bytes, pst, /*defer_reduce=*/!two));
+        }
         const bool pend = ctmi_wgrad_pending();
         RC(linear_dgrad(dqkv, b->wqkv, W(W_DLN1), T, 3 * H, H, CTMI_EPI_NONE, nullptr, post ? W(W_DH1) : nullptr, dt, pend ? nullptr : gr->splitk_ws, pend ? 0 : gr->splitk_ws_bytes, main_st, w_io));
         int np1 = 0, ns1 = 2;
@@ -314,44 +330,6 @@ extern "C" int ctmi_bloom_block_bwd(const ctmi_bloom_block* b, const ctmi_bloom_
         job(WF(W_LNP1), ns1 * H, np1, gr->dln1_w, H);
         job(WF(W_LNP1) + H, ns1 * H, np1, gr->dln1_b, H);
         return CTMI_OK;
-    }
-    // ---- MLP: out = res2 + W2 gelu(W1 ln2 + b1) + b2
-    RC(fork());
-    RC(linear_wgrad(dout, s.at(CTMI_BLK_G), gr->dw2, T, H, 4 * H, dt, pws, pws_bytes, pst, wio));
-    RC(linear_dgrad(dout, b->w2, W(W_DU), T, H, 4 * H, CTMI_BLOCK_GELUG ? CTMI_EPI_MUL : CTMI_EPI_DGELU, s.at(CTMI_BLK_U), nullptr, dt, nullptr, 0, main_st, w_io));        // modeling_bloom.py:348-363 fused
-    RC(fork());
-    RC(linear_wgrad(W(W_DU), s.at(CTMI_BLK_LN2), gr->dw1, T, 4 * H, H, dt, pws, pws_bytes, pst, wio));
-    RC(colsum_job(W(W_DU), 4 * H, W_CS_DU, gr->db1));
-    RC(linear_dgrad(W(W_DU), b->w1, W(W_DLN2), T, 4 * H, H, CTMI_EPI_NONE, nullptr, post ? dout : nullptr, dt, gr->splitk_ws, gr->splitk_ws_bytes, main_st, w_io));
-    int np2 = 0, ns2 = 2;
-    RC(ctmi_ln_bwd_parts_internal(W(W_DLN2), s.at(CTMI_BLK_H1), b->ln2_w, s.at<float>(CTMI_BLK_MEAN2), s.at<float>(CTMI_BLK_RSTD2),
-                                  post ? nullptr : dout, W(W_DH1), WF(W_LNP2), T, H, dt, 1, &np2, &ns2, main_st));
-    job(WF(W_LNP2), ns2 * H, np2, gr->dln2_w, H);
-    job(WF(W_LNP2) + H, ns2 * H, np2, gr->dln2_b, H);
-    // ---- attention: h1 = res1 + Wd att + bd
-    RC(fork());
-    // bias gradients of the two [T,H]-output Linears: column sums of dout (4h->h) and of dh1 (dense)
-    if (ns2 == 4 && !post) job(WF(W_LNP2) + 2 * H, ns2 * H, np2, gr->db2, H);
-    else RC(colsum_job(dout, H, W_CS_DOUT, gr->db2));
-    if (ns2 == 4) job(WF(W_LNP2) + 3 * H, ns2 * H, np2, gr->dbd, H);
-    else RC(colsum_job(W(W_DH1), H, W_CS_DH1, gr->dbd));
-    RC(linear_wgrad(W(W_DH1), s.at(CTMI_BLK_ATT), gr->dwd, T, H, H, dt, pws, pws_bytes, pst, wio));
-    RC(linear_dgrad(W(W_DH1), b->wd, W(W_DATT), T, H, H, CTMI_EPI_NONE, nullptr, nullptr, dt, gr->splitk_ws, gr->splitk_ws_bytes, main_st, w_io));
-    const ctmi_attn_desc d = fused_qkv_desc(b);
-    char* qkv = s.at<char>(CTMI_BLK_QKV);
-    char* dqkv = reinterpret_cast<char*>(W(W_DQKV));
-    RC(ctmi_attn_bwd(qkv, qkv + qkv_part(b, 1) * e, qkv + qkv_part(b, 2) * e, s.at(CTMI_BLK_ATT), W(W_DATT), s.at<float>(CTMI_BLK_STAT_M), s.at<float>(CTMI_BLK_STAT_L),
-                     dqkv, dqkv + qkv_part(b, 1) * e, dqkv + qkv_part(b, 2) * e, WF(W_DELTA), b->slopes, b->kpos, b->kvalid, b->first_valid, nullptr, &d, dt, main_st));
-    RC(fork());
-    RC(linear_wgrad(dqkv, s.at(CTMI_BLK_LN1), gr->dwqkv, T, 3 * H, H, dt, pws, pws_bytes, pst, wio));
-    RC(colsum_job(dqkv, 3 * H, W_CS_DQKV, gr->dbqkv));
-    RC(linear_dgrad(dqkv, b->wqkv, W(W_DLN1), T, 3 * H, H, CTMI_EPI_NONE, nullptr, post ? W(W_DH1) : nullptr, dt, gr->splitk_ws, gr->splitk_ws_bytes, main_st, w_io));
-    int np1 = 0, ns1 = 2;
-    RC(ctmi_ln_bwd_parts_internal(W(W_DLN1), b->x, b->ln1_w, s.at<float>(CTMI_BLK_MEAN1), s.at<float>(CTMI_BLK_RSTD1),
-                                  post ? nullptr : W(W_DH1), gr->dx, WF(W_LNP1), T, H, dt, 0, &np1, &ns1, main_st));
-    job(WF(W_LNP1), ns1 * H, np1, gr->dln1_w, H);
-    job(WF(W_LNP1) + H, ns1 * H, np1, gr->dln1_b, H);
-    return CTMI_OK;
     }();
     // ---- join (also after a failed launch): everything downstream (autograd accumulation, hooks, optimizer, the caller's frees)
     // is ordered on the main stream

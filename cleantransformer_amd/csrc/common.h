@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <stdarg.h>
 #include "../../include/ctmi355.h"
 
@@ -185,5 +186,7 @@ static inline uint32_t ctmi_drop_threshold(float p) {                  // p in [
     return t <= 0.0 ? 0u : (t >= 4294967295.0 ? 4294967295u : (uint32_t)t);
 }
 
+// environment switch: atoi of its value, `dflt` when unset.  Read once per site: `static const int v = ctmi_env_int("CTMI_X", 1);`
+static inline int ctmi_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -1453,8 +1453,7 @@ __global__ __launch_bounds__(256) void adamw_flat_k(MTFlat pk, AdamHyper hv, con
     }
 }
 static int adamw_form() {                                   // CTMI_ADAMW_FLAT=0: the (stride loop, tensor) grid of rounds 1-5, for A/B runs
-    static int f = -1;
-    if (f < 0) { const char* e = getenv("CTMI_ADAMW_FLAT"); f = e ? atoi(e) : 1; }
+    static const int f = ctmi_env_int("CTMI_ADAMW_FLAT", 1);
     return f;
 }
 

@@ -1348,8 +1348,7 @@ static void glds_launch(GemmArgs& g, hipStream_t st) {
     const int64_t nwork = cdiv64(g.M, BM) * cdiv64(g.N, BN) * g.splits;
     // persistent launch: one resident workgroup per occupancy slot (256 CUs x workgroups that fit a CU's 160 KiB LDS),
     // each walking work items bid, bid+G, ... with its DMA stream prefetching across item boundaries
-    static int persist_env = -2;                                            // CTMI_GEMM_PERSIST overrides the policy (experiments)
-    if (persist_env == -2) { const char* e = getenv("CTMI_GEMM_PERSIST"); persist_env = e ? atoi(e) : -1; }
+    static const int persist_env = ctmi_env_int("CTMI_GEMM_PERSIST", -1);   // overrides the policy (experiments)
     const int persist = persist_env >= 0 ? persist_env : (shared_mode() ? 0 : 1);
     // CTMI_GEMM_RESERVE_CUS = R leaves R of the 256 CUs out of every persistent launch.  A persistent GEMM owns each CU it
     // runs on until it ends (all LDS, all VGPRs), so with R = 0 a concurrent RCCL all-reduce kernel makes no progress for
@@ -1362,8 +1361,7 @@ static void glds_launch(GemmArgs& g, hipStream_t st) {
     // tile, nothing against a 256-K-step tile, and workgroups that the dispatcher starts in order stay closer together than persistent ones
     // that drift over 15 tiles each — the four column tiles that share a dlogits panel of the LM-head weight gradient then find it in their
     // XCD's L2: FETCH 13.2 -> 8.6 GB per launch, 3.47 -> 3.45 ms (profiles/r05_lmhead_wgrad_launch.txt).  CTMI_GEMM_PERSIST_KSTEPS overrides (0: no limit).
-    static int persist_ksteps = -1;
-    if (persist_ksteps < 0) { const char* e = getenv("CTMI_GEMM_PERSIST_KSTEPS"); persist_ksteps = e ? atoi(e) : 128; }
+    static const int persist_ksteps = ctmi_env_int("CTMI_GEMM_PERSIST_KSTEPS", 128);
     const bool long_tiles = persist_ksteps > 0 && g.k_per_split / 32 > persist_ksteps;
     const unsigned grid = (unsigned)((persist && !long_tiles && nwork > slots) ? slots : nwork);
     if constexpr (std::is_same<TE, f16_t>::value) {
@@ -1407,14 +1405,14 @@ extern std::atomic<int> g_ctmi_policy_shared, g_ctmi_policy_reserve;
 // RCCL channel starts on the next free one
 static int shared_level() {
     int v = g_ctmi_policy_shared.load(std::memory_order_relaxed);
-    if (v < 0) { const char* e = getenv("CTMI_GEMM_SHARED"); v = e ? std::max(0, std::min(2, atoi(e))) : 0; g_ctmi_policy_shared.store(v, std::memory_order_relaxed); }
+    if (v < 0) { v = std::max(0, std::min(2, ctmi_env_int("CTMI_GEMM_SHARED", 0))); g_ctmi_policy_shared.store(v, std::memory_order_relaxed); }
     return v;
 }
 static bool shared_mode() { return shared_level() >= 1; }
 static bool shared_tiles() { return shared_level() == 1; }
 static int reserved_cus() {
     int v = g_ctmi_policy_reserve.load(std::memory_order_relaxed);
-    if (v < 0) { const char* e = getenv("CTMI_GEMM_RESERVE_CUS"); v = e ? std::max(0, std::min(128, atoi(e))) : 0; g_ctmi_policy_reserve.store(v, std::memory_order_relaxed); }
+    if (v < 0) { v = std::max(0, std::min(128, ctmi_env_int("CTMI_GEMM_RESERVE_CUS", 0))); g_ctmi_policy_reserve.store(v, std::memory_order_relaxed); }
     return v;
 }
 #if CTMI_GEMM_HAS(0)
@@ -1436,27 +1434,22 @@ constexpr int64_t WGRAD_ITEMS = 256;     // round-3 rule (CTMI_WGRAD_RULE=0): sp
 // 1 = 128x256 ping-pong unsplit, 2 (default since round 4) = the same with split-K up to CTMI_WGRAD_ITEMS4 (128) work items: at Bloom-560M the
 // QKV gradient (96 tiles) splits two ways, the dense one (32 tiles) four ways, the two [4H,H] ones (128 tiles) stay whole
 static int wgrad_rule() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("CTMI_WGRAD_RULE"); v = e ? std::max(0, atoi(e)) : 2; }
+    static const int v = std::max(0, ctmi_env_int("CTMI_WGRAD_RULE", 2));
     return v;
 }
 static int64_t wgrad_items4() {
-    static int64_t v = -1;
-    if (v < 0) { const char* e = getenv("CTMI_WGRAD_ITEMS4"); v = e ? std::max(1, atoi(e)) : 128; }
+    static const int v = std::max(1, ctmi_env_int("CTMI_WGRAD_ITEMS4", 128));
     return v;
 }
 // smallest number of 256x256 output tiles for which a forward / data-gradient GEMM takes the 256-row ping-pong tile (below: 128x256 if
 // that fills the chip).  350 since round 1 (384 = the QKV forward: 1.5 rounds of 256 CUs on tile 3, 3 full rounds of 768 on tile 4);
 // CTMI_TILE3_MIN overrides it for sweeps — every rule of rounds 1-3 was measured with the K-loop drain of the cross-lane kernels in place.
 static int64_t tile3_min() {
-    static int64_t v = -1;
-    if (v < 0) { const char* e = getenv("CTMI_TILE3_MIN"); v = e ? std::max(1, atoi(e)) : 350; }
+    static const int v = std::max(1, ctmi_env_int("CTMI_TILE3_MIN", 350));
     return v;
 }
 static void pick_tile(int64_t M, int64_t N, int64_t K, bool wgrad, bool bkm, int epi, int max_splits, int& tile, int& splits) {
-    static int force = -2, force_split = -2;
-    if (force == -2) { const char* e = getenv("CTMI_GEMM_TILE"); force = e ? atoi(e) : -1; }
-    if (force_split == -2) { const char* e = getenv("CTMI_GEMM_SPLIT"); force_split = e ? atoi(e) : -1; }
+    static const int force = ctmi_env_int("CTMI_GEMM_TILE", -1), force_split = ctmi_env_int("CTMI_GEMM_SPLIT", -1);
     if (force_split >= 1) max_splits = std::min(max_splits, force_split);
     const int64_t t0 = cdiv64(M, 128) * cdiv64(N, 128), t1 = cdiv64(M, 256) * cdiv64(N, 128), t2 = cdiv64(M, 256) * cdiv64(N, 256);
     const int64_t t4 = cdiv64(M, 128) * cdiv64(N, 256);
@@ -1477,8 +1470,7 @@ static void pick_tile(int64_t M, int64_t N, int64_t K, bool wgrad, bool bkm, int
         return;
     }
     if (wgrad) {
-        static int nosplit = -1;
-        if (nosplit < 0) { const char* e = getenv("CTMI_WGRAD_NOSPLIT"); nosplit = e ? atoi(e) : 0; }
+        static const int nosplit = ctmi_env_int("CTMI_WGRAD_NOSPLIT", 0);
         // LM head: [V,H] — and its row windows: the data-parallel path produces the tied gradient in <= 64 MiB pieces of 15 360 / 16 384
         // rows (trainer/ddp.py chunk_rows: whole rounds of the CUs the policy leaves), 240 / 256 tiles of 256x256; the layer weight
         // gradients of this geometry have <= 64 such tiles (round-3 advisor: a piece used to fall to the unsplit 128x128 rule below)
@@ -1523,9 +1515,8 @@ static void pick_tile(int64_t M, int64_t N, int64_t K, bool wgrad, bool bkm, int
 }
 
 static bool glds_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("CTMI_GEMM_GLDS"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v == 1;
+    static const bool on = [] { const char* e = getenv("CTMI_GEMM_GLDS"); return !(e && e[0] == '0'); }();      // (its own rule: only a leading '0' turns it off)
+    return on;
 }
 
 template <typename T, typename TO, bool AK, bool BKM, int EPI>
@@ -1533,7 +1524,7 @@ static int gemm_launch(GemmArgs& g, bool fast, hipStream_t st) {
     using TA = OpTile<T, AK, Tile<T>::BM>;
     using TB = OpTile<T, BKM, Tile<T>::BN>;
     const size_t lds = 2 * (size_t)(TA::ELEMS + TB::ELEMS) * sizeof(T);
-    const unsigned grid = (unsigned)(g.tiles_m * g.tiles_n * g.splits);
+    bool glds = false;
     if constexpr (std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value) {   // the LDS-DMA family: bf16 and (round 5) fp16; fp32 takes the register-staged kernel below
         if (fast && glds_enabled() && g.K % 32 == 0) {
             int tile, splits;
@@ -1553,33 +1544,30 @@ static int gemm_launch(GemmArgs& g, bool fast, hipStream_t st) {
             bool xl = false;
             if constexpr (CAN_XLANE) xl = tile == 3 && !g.nt_c && !res && g.vec8;
             if (xl) { if constexpr (CAN_XLANE) glds_launch<T, TO, AK, BKM, EPI, 8, 4, true, false, true>(g, st); }
-            else if (tile == 3) { if constexpr (CAN_RES) { if (res) glds_launch<T, TO, AK, BKM, EPI, 8, 4, true, true>(g, st); else glds_launch<T, TO, AK, BKM, EPI, 8, 4, true>(g, st); }
-                             else glds_launch<T, TO, AK, BKM, EPI, 8, 4, true>(g, st); }
-            else if (tile == 4) { if constexpr (CAN_RES) { if (res) glds_launch<T, TO, AK, BKM, EPI, 4, 4, true, true>(g, st); else glds_launch<T, TO, AK, BKM, EPI, 4, 4, true>(g, st); }
-                                  else glds_launch<T, TO, AK, BKM, EPI, 4, 4, true>(g, st); }
+            else if (tile == 3 && res) { if constexpr (CAN_RES) glds_launch<T, TO, AK, BKM, EPI, 8, 4, true, true>(g, st); }
+            else if (tile == 3) glds_launch<T, TO, AK, BKM, EPI, 8, 4, true>(g, st);
+            else if (tile == 4 && res) { if constexpr (CAN_RES) glds_launch<T, TO, AK, BKM, EPI, 4, 4, true, true>(g, st); }
+            else if (tile == 4) glds_launch<T, TO, AK, BKM, EPI, 4, 4, true>(g, st);
             else if (tile == 2) glds_launch<T, TO, AK, BKM, EPI, 8, 4>(g, st);
             else if (tile == 1) glds_launch<T, TO, AK, BKM, EPI, 8, 2>(g, st);
             else glds_launch<T, TO, AK, BKM, EPI, 4, 2>(g, st);
             CTMI_CHECK_LAUNCH("gemm_glds");
-            if (g.splits > 1) {
-                const int64_t total = g.M * g.N;
-                const unsigned rg = (unsigned)std::min<int64_t>(cdiv64(total, 256), 4096);
-                hipLaunchKernelGGL((splitk_reduce<TO>), dim3(rg), dim3(256), 0, st, g.slabs, reinterpret_cast<TO*>(g.C), g.ldc, g.M, g.N, g.splits, g.alpha, g.beta);
-                CTMI_CHECK_LAUNCH("gemm_splitk_reduce");
-            }
-            return CTMI_OK;
+            glds = true;
         }
     }
-    if (fast) {
-        auto kern = &gemm_kernel<T, TO, AK, BKM, EPI, true>;
-        ctmi_dyn_lds(reinterpret_cast<const void*>(kern), lds);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, g);
-    } else {
-        auto kern = &gemm_kernel<T, TO, AK, BKM, EPI, false>;
-        ctmi_dyn_lds(reinterpret_cast<const void*>(kern), lds);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, g);
+    if (!glds) {
+        const unsigned grid = (unsigned)(g.tiles_m * g.tiles_n * g.splits);
+        if (fast) {
+            auto kern = &gemm_kernel<T, TO, AK, BKM, EPI, true>;
+            ctmi_dyn_lds(reinterpret_cast<const void*>(kern), lds);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, g);
+        } else {
+            auto kern = &gemm_kernel<T, TO, AK, BKM, EPI, false>;
+            ctmi_dyn_lds(reinterpret_cast<const void*>(kern), lds);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, g);
+        }
+        CTMI_CHECK_LAUNCH("gemm");
     }
-    CTMI_CHECK_LAUNCH("gemm");
     if (g.splits > 1) {
         const int64_t total = g.M * g.N;
         const unsigned rg = (unsigned)std::min<int64_t>(cdiv64(total, 256), 4096);
@@ -1608,31 +1596,39 @@ static int gemm_unsupported(int ak, int bk, int epi, int out_f32) {
     return CTMI_ERR_UNSUPPORTED;
 }
 
-#if CTMI_GEMM_HAS(1)
-int ctmi_gemm_bf16_nt(GemmArgs& g, int epi, bool fast, hipStream_t st) {
-    if (epi == CTMI_EPI_NONE) return gemm_launch<bf16_t, bf16_t, false, false, CTMI_EPI_NONE>(g, fast, st);
-    if (epi == CTMI_EPI_GELU) return gemm_launch<bf16_t, bf16_t, false, false, CTMI_EPI_GELU>(g, fast, st);
-    if (epi == CTMI_EPI_GELUG) return gemm_launch<bf16_t, bf16_t, false, false, CTMI_EPI_GELUG>(g, fast, st);
-    if (epi == CTMI_EPI_RELU) return gemm_launch<bf16_t, bf16_t, false, false, CTMI_EPI_RELU>(g, fast, st);
-    if (epi == CTMI_EPI_DGELU) return gemm_launch<bf16_t, bf16_t, false, false, CTMI_EPI_DGELU>(g, fast, st);   // data gradient through an [in,out] (Conv1D) weight
-    return gemm_unsupported(0, 0, epi, 0);
+// one routine per operand layout: the epilogues it accepts.  Each is instantiated by the parts that own its (T, TO) pairs
+template <typename T, typename TO>
+static int gemm_nt(GemmArgs& g, int epi, bool fast, hipStream_t st) {                 // forward: x W^T
+    if (epi == CTMI_EPI_NONE) return gemm_launch<T, TO, false, false, CTMI_EPI_NONE>(g, fast, st);
+    if (epi == CTMI_EPI_GELU) return gemm_launch<T, TO, false, false, CTMI_EPI_GELU>(g, fast, st);
+    if (epi == CTMI_EPI_GELUG) return gemm_launch<T, TO, false, false, CTMI_EPI_GELUG>(g, fast, st);
+    if (epi == CTMI_EPI_RELU) return gemm_launch<T, TO, false, false, CTMI_EPI_RELU>(g, fast, st);
+    if (epi == CTMI_EPI_DGELU) return gemm_launch<T, TO, false, false, CTMI_EPI_DGELU>(g, fast, st);   // data gradient through an [in,out] (Conv1D) weight
+    return gemm_unsupported(0, 0, epi, std::is_same<T, float>::value ? 1 : 0);
 }
-#endif
-#if CTMI_GEMM_HAS(2)
-int ctmi_gemm_bf16_nn(GemmArgs& g, int epi, bool fast, hipStream_t st) {
-    if (epi == CTMI_EPI_NONE) return gemm_launch<bf16_t, bf16_t, false, true, CTMI_EPI_NONE>(g, fast, st);
-    if (epi == CTMI_EPI_DGELU) return gemm_launch<bf16_t, bf16_t, false, true, CTMI_EPI_DGELU>(g, fast, st);
-    if (epi == CTMI_EPI_MUL) return gemm_launch<bf16_t, bf16_t, false, true, CTMI_EPI_MUL>(g, fast, st);
-    if (epi == CTMI_EPI_DRELU) return gemm_launch<bf16_t, bf16_t, false, true, CTMI_EPI_DRELU>(g, fast, st);
-    if (epi == CTMI_EPI_GELU) return gemm_launch<bf16_t, bf16_t, false, true, CTMI_EPI_GELU>(g, fast, st);     // forward through an [in,out] (Conv1D) weight
-    return gemm_unsupported(0, 1, epi, 0);
+template <typename T, typename TO>
+static int gemm_nn(GemmArgs& g, int epi, bool fast, hipStream_t st) {                 // data gradient: dy W
+    if (epi == CTMI_EPI_NONE) return gemm_launch<T, TO, false, true, CTMI_EPI_NONE>(g, fast, st);
+    if (epi == CTMI_EPI_DGELU) return gemm_launch<T, TO, false, true, CTMI_EPI_DGELU>(g, fast, st);
+    if (epi == CTMI_EPI_MUL) return gemm_launch<T, TO, false, true, CTMI_EPI_MUL>(g, fast, st);
+    if (epi == CTMI_EPI_DRELU) return gemm_launch<T, TO, false, true, CTMI_EPI_DRELU>(g, fast, st);
+    if (epi == CTMI_EPI_GELU) return gemm_launch<T, TO, false, true, CTMI_EPI_GELU>(g, fast, st);     // forward through an [in,out] (Conv1D) weight
+    return gemm_unsupported(0, 1, epi, std::is_same<T, float>::value ? 1 : 0);
 }
-#endif
-#if CTMI_GEMM_HAS(3)
-int ctmi_gemm_bf16_tn(GemmArgs& g, int epi, bool fast, hipStream_t st) {
-    if (epi == CTMI_EPI_NONE) return gemm_launch<bf16_t, float, true, true, CTMI_EPI_NONE>(g, fast, st);
+template <typename T>
+static int gemm_tn(GemmArgs& g, int epi, bool fast, hipStream_t st) {                 // weight gradient: dy^T x, fp32 output
+    if (epi == CTMI_EPI_NONE) return gemm_launch<T, float, true, true, CTMI_EPI_NONE>(g, fast, st);
     return gemm_unsupported(1, 1, epi, 1);
 }
+
+#if CTMI_GEMM_HAS(1)
+int ctmi_gemm_bf16_nt(GemmArgs& g, int epi, bool fast, hipStream_t st) { return gemm_nt<bf16_t, bf16_t>(g, epi, fast, st); }
+#endif
+#if CTMI_GEMM_HAS(2)
+int ctmi_gemm_bf16_nn(GemmArgs& g, int epi, bool fast, hipStream_t st) { return gemm_nn<bf16_t, bf16_t>(g, epi, fast, st); }
+#endif
+#if CTMI_GEMM_HAS(3)
+int ctmi_gemm_bf16_tn(GemmArgs& g, int epi, bool fast, hipStream_t st) { return gemm_tn<bf16_t>(g, epi, fast, st); }
 
 // ---- grouped weight gradients: host side -----------------------------------------------------------------------------------------------------
 #include <map>
@@ -1709,8 +1705,7 @@ void build_items(const WgShape& sh, std::vector<int4>& out, int& nitems, int& ns
 // CTMI_WGRAD_GROUP: 0 = off (four launches per block, split-K slabs: round 4), 1 (default) = grouped, the tiles of the last partial round cut in two
 // along K (partials in the workspace + a small second launch), 2 = every tile cut in two (experiments), 3 = grouped, nothing cut
 int ctmi_wgrad_group_mode() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("CTMI_WGRAD_GROUP"); v = e ? std::max(0, atoi(e)) : 1; }
+    static const int v = std::max(0, ctmi_env_int("CTMI_WGRAD_GROUP", 1));
     return v;
 }
 
@@ -1850,68 +1845,31 @@ int ctmi_wgrad_grouped_ex(const ctmi_wgrad_problem* pr, int n, int64_t T, int dt
 #endif
 
 #if CTMI_GEMM_HAS(4)
-int ctmi_gemm_f16_nt(GemmArgs& g, int epi, bool fast, hipStream_t st) {
-    using T = f16_t;
-    if (epi == CTMI_EPI_NONE) return gemm_launch<T, T, false, false, CTMI_EPI_NONE>(g, fast, st);
-    if (epi == CTMI_EPI_GELU) return gemm_launch<T, T, false, false, CTMI_EPI_GELU>(g, fast, st);
-    if (epi == CTMI_EPI_GELUG) return gemm_launch<T, T, false, false, CTMI_EPI_GELUG>(g, fast, st);
-    if (epi == CTMI_EPI_RELU) return gemm_launch<T, T, false, false, CTMI_EPI_RELU>(g, fast, st);
-    if (epi == CTMI_EPI_DGELU) return gemm_launch<T, T, false, false, CTMI_EPI_DGELU>(g, fast, st);
-    return gemm_unsupported(0, 0, epi, 0);
-}
+int ctmi_gemm_f16_nt(GemmArgs& g, int epi, bool fast, hipStream_t st) { return gemm_nt<f16_t, f16_t>(g, epi, fast, st); }
 #endif
 #if CTMI_GEMM_HAS(5)
-int ctmi_gemm_f16_nn(GemmArgs& g, int epi, bool fast, hipStream_t st) {
-    using T = f16_t;
-    if (epi == CTMI_EPI_NONE) return gemm_launch<T, T, false, true, CTMI_EPI_NONE>(g, fast, st);
-    if (epi == CTMI_EPI_DGELU) return gemm_launch<T, T, false, true, CTMI_EPI_DGELU>(g, fast, st);
-    if (epi == CTMI_EPI_MUL) return gemm_launch<T, T, false, true, CTMI_EPI_MUL>(g, fast, st);
-    if (epi == CTMI_EPI_DRELU) return gemm_launch<T, T, false, true, CTMI_EPI_DRELU>(g, fast, st);
-    if (epi == CTMI_EPI_GELU) return gemm_launch<T, T, false, true, CTMI_EPI_GELU>(g, fast, st);
-    return gemm_unsupported(0, 1, epi, 0);
-}
+int ctmi_gemm_f16_nn(GemmArgs& g, int epi, bool fast, hipStream_t st) { return gemm_nn<f16_t, f16_t>(g, epi, fast, st); }
 #endif
 #if CTMI_GEMM_HAS(6)
-int ctmi_gemm_f16_tn(GemmArgs& g, int epi, bool fast, hipStream_t st) {
-    if (epi == CTMI_EPI_NONE) return gemm_launch<f16_t, float, true, true, CTMI_EPI_NONE>(g, fast, st);
-    return gemm_unsupported(1, 1, epi, 1);
-}
+int ctmi_gemm_f16_tn(GemmArgs& g, int epi, bool fast, hipStream_t st) { return gemm_tn<f16_t>(g, epi, fast, st); }
 #endif
 
 #if CTMI_GEMM_HAS(0)
-static int gemm_dispatch_bf16(GemmArgs& g, int ak, int bk, int epi, int out_f32, bool fast, hipStream_t st) {
-    if (!ak && !bk && !out_f32) return ctmi_gemm_bf16_nt(g, epi, fast, st);
-    if (!ak && bk && !out_f32) return ctmi_gemm_bf16_nn(g, epi, fast, st);
-    if (ak && bk && out_f32) return ctmi_gemm_bf16_tn(g, epi, fast, st);
-    return gemm_unsupported(ak, bk, epi, out_f32);
-}
-
-// fp16 storage (round 5): the same layouts, epilogues and tile families as bf16 (translation-unit parts 4 / 5 / 6)
-static int gemm_dispatch_f16(GemmArgs& g, int ak, int bk, int epi, int out_f32, bool fast, hipStream_t st) {
-    if (!ak && !bk && !out_f32) return ctmi_gemm_f16_nt(g, epi, fast, st);
-    if (!ak && bk && !out_f32) return ctmi_gemm_f16_nn(g, epi, fast, st);
-    if (ak && bk && out_f32) return ctmi_gemm_f16_tn(g, epi, fast, st);
-    return gemm_unsupported(ak, bk, epi, out_f32);
-}
-
-static int gemm_dispatch_f32(GemmArgs& g, int ak, int bk, int epi, bool fast, hipStream_t st) {   // fp32 storage: output is fp32 either way
-    using T = float;
-    if (!ak && !bk) {
-        if (epi == CTMI_EPI_NONE) return gemm_launch<T, float, false, false, CTMI_EPI_NONE>(g, fast, st);
-        if (epi == CTMI_EPI_GELU) return gemm_launch<T, float, false, false, CTMI_EPI_GELU>(g, fast, st);
-        if (epi == CTMI_EPI_GELUG) return gemm_launch<T, float, false, false, CTMI_EPI_GELUG>(g, fast, st);
-        if (epi == CTMI_EPI_RELU) return gemm_launch<T, float, false, false, CTMI_EPI_RELU>(g, fast, st);
-        if (epi == CTMI_EPI_DGELU) return gemm_launch<T, float, false, false, CTMI_EPI_DGELU>(g, fast, st);
+// fp32 storage (instantiated here): output is fp32 either way.  bf16 / fp16 storage: the same layouts in their own parts, NT and NN with
+// an output of the storage type, TN with an fp32 output
+static int gemm_dispatch(GemmArgs& g, int dtype, int ak, int bk, int epi, int out_f32, bool fast, hipStream_t st) {
+    const bool nt = !ak && !bk, nn = !ak && bk, tn = ak && bk;
+    if (dtype == CTMI_F32) {
+        if (nt) return gemm_nt<float, float>(g, epi, fast, st);
+        if (nn) return gemm_nn<float, float>(g, epi, fast, st);
+        if (tn) return gemm_tn<float>(g, epi, fast, st);
+        return gemm_unsupported(ak, bk, epi, 1);
     }
-    if (!ak && bk) {
-        if (epi == CTMI_EPI_NONE) return gemm_launch<T, float, false, true, CTMI_EPI_NONE>(g, fast, st);
-        if (epi == CTMI_EPI_DGELU) return gemm_launch<T, float, false, true, CTMI_EPI_DGELU>(g, fast, st);
-        if (epi == CTMI_EPI_MUL) return gemm_launch<T, float, false, true, CTMI_EPI_MUL>(g, fast, st);
-        if (epi == CTMI_EPI_DRELU) return gemm_launch<T, float, false, true, CTMI_EPI_DRELU>(g, fast, st);
-        if (epi == CTMI_EPI_GELU) return gemm_launch<T, float, false, true, CTMI_EPI_GELU>(g, fast, st);
-    }
-    if (ak && bk && epi == CTMI_EPI_NONE) return gemm_launch<T, float, true, true, CTMI_EPI_NONE>(g, fast, st);
-    return gemm_unsupported(ak, bk, epi, 1);
+    const bool h = dtype == CTMI_F16;
+    if (nt && !out_f32) return h ? ctmi_gemm_f16_nt(g, epi, fast, st) : ctmi_gemm_bf16_nt(g, epi, fast, st);
+    if (nn && !out_f32) return h ? ctmi_gemm_f16_nn(g, epi, fast, st) : ctmi_gemm_bf16_nn(g, epi, fast, st);
+    if (tn && out_f32) return h ? ctmi_gemm_f16_tn(g, epi, fast, st) : ctmi_gemm_bf16_tn(g, epi, fast, st);
+    return gemm_unsupported(ak, bk, epi, out_f32);
 }
 
 extern "C" int ctmi_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor,
@@ -1944,8 +1902,7 @@ extern "C" int ctmi_gemm(const void* A, int64_t lda, int a_kmajor, const void* B
     auto al = [](const void* p, int bytes) { return p == nullptr || ((((uintptr_t)p) & (bytes - 1)) == 0); };
     const int cbytes = (out_f32 || dtype == CTMI_F32) ? 16 : 8;
     g.vec_c = (ldc % 4 == 0) && al(C, cbytes) && al(residual, 4 * es) && al(aux_in, 4 * es) && al(aux_out, 4 * es) && al(bias, 16);
-    static int nt_on = -1;
-    if (nt_on < 0) { const char* e = getenv("CTMI_GEMM_NT"); nt_on = e ? atoi(e) : 1; }
+    static const int nt_on = ctmi_env_int("CTMI_GEMM_NT", 1);
     g.nt_c = nt_on && (M * N * (int64_t)((out_f32 || dtype == CTMI_F32) ? 4 : 2) > (1LL << 30)) ? 1 : 0;
     g.vec8 = g.vec_c && (ldc % 8 == 0) && al(C, 16) && al(residual, 16) && al(aux_in, 16) && al(aux_out, 16);   // 8-element rows (LDS-shuffled epilogue)
     // split-K: only for plain accumulations (weight gradients) that would leave most of the 256 CUs idle
@@ -1962,9 +1919,7 @@ extern "C" int ctmi_gemm(const void* A, int64_t lda, int a_kmajor, const void* B
             if (g.splits <= 1) { g.splits = 1; g.k_per_split = K; g.slabs = nullptr; }
         }
     }
-    if (dtype == CTMI_F32) return gemm_dispatch_f32(g, a_kmajor, b_kmajor, epilogue, fast, as_stream(stream));
-    if (dtype == CTMI_F16) return gemm_dispatch_f16(g, a_kmajor, b_kmajor, epilogue, out_f32, fast, as_stream(stream));
-    return gemm_dispatch_bf16(g, a_kmajor, b_kmajor, epilogue, out_f32, fast, as_stream(stream));
+    return gemm_dispatch(g, dtype, a_kmajor, b_kmajor, epilogue, out_f32, fast, as_stream(stream));
 }
 #endif  // CTMI_GEMM_HAS(0)
 

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import math
 import os as _os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -105,25 +105,41 @@ class _AttnCtx:
 _NP = len(_lib.BLK_PARAMS)      # a block node's arguments: x, these 12 parameters, (the per-op node: 6 adapter tensors or None,) then the non-tensor options
 
 
+class BlockSpec(NamedTuple):
+    """What a model tells the fused block node about its block (the parameters follow _lib.BLK_PARAMS order for every model)."""
+    mask: ops.MaskInfo
+    nh: int
+    eps: float
+    slopes: Optional[Tensor] = None          # ALiBi slopes, or None: no position bias in the scores
+    post_ln_res: bool = False
+    flags: int = 0                           # _lib.BLK_*: layout of the QKV activation and of the weights / weight gradients
+    attn_scale: float = 0.0                  # 0 = 1 / sqrt(head_dim)
+    future_fill: float = 0.0                 # 0 = finfo.min
+    kv_blocked: bool = False                 # the presents are views of a q | k | v activation (else head-interleaved)
+    side_stream_override: bool = False       # _WGRAD_SIDE_STREAM applies (Bloom: bench.py's breakdown pass sets it)
+
+
 class BloomBlockFn(torch.autograd.Function):
     """modeling_bloom.py:142-159 (+ 76-124, 255-271) forward and its full backward: ONE autograd node and ONE library call
-    per direction (ctmi_bloom_block_fwd / ctmi_bloom_block_bwd run the fixed kernel sequences; include/ctmi355.h)."""
+    per direction (ctmi_bloom_block_fwd / ctmi_bloom_block_bwd run the fixed kernel sequences; include/ctmi355.h).  The pre-LN GPT-2/3
+    block is the same node with its own BlockSpec (modeling_gpt.py).  Arguments: x, the 12 parameters, the spec, the KVOut."""
 
     @staticmethod
     def forward(ctx, x, *args):
-        ps, (actx, eps, post_ln_res, kv_out) = args[:_NP], args[_NP:]
+        ps, (spec, kv_out) = args[:_NP], args[_NP:]
         B, S, H = x.shape
         x2 = ops._c(x.reshape(B * S, H))
-        acts = ops.bloom_block_fwd(x2, ops.block_params(ps, x.dtype), actx.mask, actx.slopes, eps, post_ln_res, B, S, actx.nh)
-        ops.note_block_params(actx.mask, ps)
+        acts = ops.bloom_block_fwd(x2, ops.block_params(ps, x.dtype), spec.mask, spec.slopes, spec.eps, spec.post_ln_res, B, S, spec.nh,
+                                   flags=spec.flags, attn_scale=spec.attn_scale, future_fill=spec.future_fill)
+        ops.note_block_params(spec.mask, ps)
         # The slab is a tensor: it goes through save_for_backward (released right after this node's backward — as a Python attribute of
         # ctx it lived as long as anything referenced the graph, i.e. through the NEXT step's forward in the reference loop); only
         # geometry stays on ctx.  Without a graph nothing is saved and the K/V presents are copied out (ops.LazyKV).
         grad = getattr(kv_out, "grad", True) and any(ctx.needs_input_grad)
         if grad:
             ctx.save_for_backward(x2, *ps, acts.slab)
-            ctx.geo, ctx.actx, ctx.eps, ctx.post_ln_res, ctx.shape = acts.geometry(), actx, eps, post_ln_res, (B, S, H)
-        kv = ops.LazyKV(acts, blocked=False, eager=not grad)
+            ctx.geo, ctx.spec, ctx.shape = acts.geometry(), spec, (B, S, H)
+        kv = ops.LazyKV(acts, blocked=spec.kv_blocked, eager=not grad)
         if grad:
             ctx.kv = kv
         kv_out.append(kv)
@@ -132,8 +148,9 @@ class BloomBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         if dout is None:
-            return (None,) * (1 + _NP + 4)
+            return (None,) * (1 + _NP + 2)
         x2, *ps, slab = ctx.saved_tensors
+        spec = ctx.spec
         B, S, H = ctx.shape
         dout2 = ops._c(dout.reshape(B * S, H))
         # Parameter gradients (wgrad GEMMs + bias column sums) feed nothing further down the backward chain: inside the
@@ -141,12 +158,12 @@ class BloomBlockFn(torch.autograd.Function):
         # back into the current stream before the call returns, so everything downstream (autograd accumulation, DDP hooks,
         # optimizer) is ordered.
         ctx.kv.release()
-        side = _WGRAD_SIDE_STREAM
+        side = _WGRAD_SIDE_STREAM if spec.side_stream_override else None
         # single process, no accumulation pending, no gradient hooks: a side stream (if one is used at all) is joined once, at the end of the backward pass
-        defer = side is not False and x2.is_cuda and ops.params_allow_deferred_grads(ps, ctx.actx.mask)
-        dx, g = ops.bloom_block_bwd(ops.BlockActs.rebuild(slab, ctx.geo), x2, ops.block_params(ps, x2.dtype), ctx.actx.mask, ctx.actx.slopes, ctx.eps,
-                                    ctx.post_ln_res, dout2, use_side_stream=side, defer_join=defer)
-        return (dx.view(B, S, H), *g, None, None, None, None)
+        defer = side is not False and x2.is_cuda and ops.params_allow_deferred_grads(ps, spec.mask)
+        dx, g = ops.bloom_block_bwd(ops.BlockActs.rebuild(slab, ctx.geo), x2, ops.block_params(ps, x2.dtype), spec.mask, spec.slopes, spec.eps,
+                                    spec.post_ln_res, dout2, use_side_stream=side, defer_join=defer)
+        return (dx.view(B, S, H), *g, None, None)
 
 
 # ------------------------------------------------------------------------------------------------ the same block, one launch per op
@@ -582,7 +599,8 @@ class BloomBlock(torch.nn.Module):
                                         (rng.next_seed(), rng.next_seed(), rng.next_seed()) if drop else (0, 0, 0), kv)
             return out, kv[0]
         kv = ops.KVOut()
-        out = BloomBlockFn.apply(hidden_states, *ps, actx, self.eps, post, kv)
+        spec = BlockSpec(actx.mask, actx.nh, self.eps, slopes=actx.slopes, post_ln_res=post, side_stream_override=True)
+        out = BloomBlockFn.apply(hidden_states, *ps, spec, kv)
         return out, kv[0]
 
     def block_params(self):

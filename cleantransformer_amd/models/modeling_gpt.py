@@ -30,7 +30,7 @@ import torch
 from .. import _lib, ops, rng
 from ..generation.generation_util import GenerationMixin
 from ..transformer import LayerNorm
-from .modeling_bloom import EmbedFn, LMHeadFn, ShiftedCrossEntropyFn, _TieCtx, _torch_dtype
+from .modeling_bloom import BlockSpec, BloomBlockFn, EmbedFn, LMHeadFn, ShiftedCrossEntropyFn, _TieCtx, _torch_dtype
 
 Tensor = torch.Tensor
 
@@ -148,45 +148,6 @@ class GPTAttnFn(torch.autograd.Function):
         return dqkv.view(out.shape[0], out.shape[1], 3 * H), None, None, None, None, None
 
 
-class GPT2BlockFn(torch.autograd.Function):
-    """One pre-LN GPT-2/3 block (modeling_gpt.py:144-149 with AttentionLayer :52-101 and the MLP :122-133) as ONE autograd node and ONE
-    library call per direction — the block-level entry point of the C ABI (ctmi_bloom_block_fwd/bwd) with the GPT-2 flags: q | k | v
-    blocked QKV activation, -1e4 future fill, optional score scaling, weights read AND weight gradients written in Conv1D's own
-    [in,out] layout (the bf16 shadows the optimizer maintains are used as they are: no transposed compute copies on this path).  Used
-    for training steps without dropout; everything else (GPT-1's post-LN order, dropout, KV-cache decode) keeps the per-op path."""
-
-    @staticmethod
-    def forward(ctx, x, n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo, mask: ops.MaskInfo, nh: int, eps: float, scale: float, kv_out: list):
-        B, S, H = x.shape
-        x2 = ops._c(x.reshape(B * S, H))
-        params = ops.block_params((n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo), x.dtype)
-        acts = ops.bloom_block_fwd(x2, params, mask, None, eps, False, B, S, nh, flags=_lib.BLK_QKV_BLOCKED | _lib.BLK_WGRAD_IN_OUT | _lib.BLK_W_IN_OUT,
-                                   attn_scale=scale, future_fill=-1e4)
-        ops.note_block_params(mask, (n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo))
-        grad = getattr(kv_out, "grad", True) and any(ctx.needs_input_grad)                                # see BloomBlockFn: slab through save_for_backward, presents lazily
-        if grad:
-            ctx.save_for_backward(x2, n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo, acts.slab)
-            ctx.geo, ctx.mask, ctx.eps, ctx.shape = acts.geometry(), mask, eps, (B, S, H)
-        kv = ops.LazyKV(acts, blocked=True, eager=not grad)
-        if grad:
-            ctx.kv = kv
-        kv_out.append(kv)
-        return acts.out.view(B, S, H)
-
-    @staticmethod
-    def backward(ctx, dout):
-        if dout is None:
-            return (None,) * 18
-        x2, n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo, slab = ctx.saved_tensors
-        B, S, H = ctx.shape
-        dout2 = ops._c(dout.reshape(B * S, H))
-        params = ops.block_params((n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo), x2.dtype)
-        ctx.kv.release()
-        defer = x2.is_cuda and ops.params_allow_deferred_grads((n1w, n1b, wa, ba, wp, bp, n2w, n2b, wf, bf, wo, bo), ctx.mask)
-        dx, g = ops.bloom_block_bwd(ops.BlockActs.rebuild(slab, ctx.geo), x2, params, ctx.mask, None, ctx.eps, False, dout2, defer_join=defer)
-        return (dx.view(B, S, H), *g, None, None, None, None, None)
-
-
 def _attend_cached(qkv: Tensor, past, mask: ops.MaskInfo, nh: int, scale: float, drop_p: float = 0.0, drop_seed: int = 0):
     """Inference with a KV cache (modeling_gpt.py:75-80): returns the context and the concatenated (k, v) [B,nh,Sk,hd]."""
     B, S, H3 = qkv.shape
@@ -300,13 +261,16 @@ class TransformerBlock(torch.nn.Module):
             output = self.norm2(self._mlp(n1, residual=n1))
         elif (k_v_past is None and torch.is_grad_enabled() and x.requires_grad
               and not (self.training and (self.attn.attn_dropout.p > 0.0 or self.attn.resid_dropout.p > 0.0 or self.mlp[3].p > 0.0))):
-            # GPT-2/3 pre-LN training step without dropout: one autograd node, one library call per direction
+            # GPT-2/3 pre-LN training step without dropout: the fused block node (one library call per direction) with the GPT-2 spelling of
+            # the block — q | k | v blocked QKV activation, -1e4 future fill, optional score scaling, weights read AND weight gradients written
+            # in Conv1D's own [in,out] layout (the optimizer's bf16 shadows are used as they are: no transposed compute copies on this path)
             a, fc, proj = self.attn, self.mlp[0], self.mlp[2]
             hd = a.n_state // a.n_head
             kv = ops.KVOut()
-            output = GPT2BlockFn.apply(x, self.norm1.weight, self.norm1.bias, a.c_attn.weight, a.c_attn.bias, a.c_proj.weight, a.c_proj.bias,
-                                       self.norm2.weight, self.norm2.bias, fc.weight, fc.bias, proj.weight, proj.bias,
-                                       attention_mask, a.n_head, self.norm1.eps, (1.0 / math.sqrt(hd)) if a.scale else 1.0, kv)
+            spec = BlockSpec(attention_mask, a.n_head, self.norm1.eps, flags=_lib.BLK_QKV_BLOCKED | _lib.BLK_WGRAD_IN_OUT | _lib.BLK_W_IN_OUT,
+                             attn_scale=(1.0 / math.sqrt(hd)) if a.scale else 1.0, future_fill=-1e4, kv_blocked=True)
+            output = BloomBlockFn.apply(x, self.norm1.weight, self.norm1.bias, a.c_attn.weight, a.c_attn.bias, a.c_proj.weight, a.c_proj.bias,
+                                        self.norm2.weight, self.norm2.bias, fc.weight, fc.bias, proj.weight, proj.bias, spec, kv)
             k_v_past = kv[0]
         else:                                                                        # GPT-2/3: pre-LN (:144-149), per-op
             x, k_v_past = self.attn(self.norm1(x), attention_mask=attention_mask, head_mask=head_mask, k_v_past=k_v_past, residual=x)

@@ -261,6 +261,13 @@ class MaskInfo:
         check(_lib.load().ctmi_mask_prep(_p(am), _p(self.kpos), _p(self.kvalid), _p(self.first_valid), B, S, _stream()),
               "mask_prep")
 
+    @staticmethod
+    def ptrs(mask: Optional["MaskInfo"], slopes: Optional[Tensor]):
+        """(kpos, kvalid, first_valid) as a kernel call takes them: the ALiBi key positions only together with slopes; all None without a mask."""
+        if mask is None:
+            return None, None, None
+        return (_p(mask.kpos) if slopes is not None else None), _p(mask.kvalid), _p(mask.first_valid)
+
 
 def _strided_desc(B, nh, Sq, Sk, hd, q_str, k_str, v_str, o_str, scale, causal, am_str=(0, 0, 0, 0), future_fill: float = 0.0,
                   dropout_p: float = 0.0, dropout_seed: int = 0) -> AttnDesc:
@@ -278,20 +285,13 @@ def _strided_desc(B, nh, Sq, Sk, hd, q_str, k_str, v_str, o_str, scale, causal, 
     return d
 
 
-def _view_ptr(t: Tensor):
-    return C.c_void_p(t.data_ptr())
-
-
 def attn_fwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, desc: AttnDesc, slopes: Optional[Tensor],
              mask: Optional[MaskInfo], add_mask: Optional[Tensor] = None):
     """q,k,v,out: tensors (possibly views) whose data_ptr is element (b=0,h=0,row=0,d=0); strides in `desc`."""
     dev = q.device
     stat_m = torch.empty((desc.B, desc.nh, desc.Sq), dtype=torch.float32, device=dev)
     stat_l = torch.empty((desc.B, desc.nh, desc.Sq), dtype=torch.float32, device=dev)
-    check(_lib.load().ctmi_attn_fwd(_view_ptr(q), _view_ptr(k), _view_ptr(v), _view_ptr(out), _p(stat_m), _p(stat_l),
-                                    _p(slopes), _p(mask.kpos) if (mask is not None and slopes is not None) else None,
-                                    _p(mask.kvalid) if mask is not None else None,
-                                    _p(mask.first_valid) if mask is not None else None,
+    check(_lib.load().ctmi_attn_fwd(_p(q), _p(k), _p(v), _p(out), _p(stat_m), _p(stat_l), _p(slopes), *MaskInfo.ptrs(mask, slopes),
                                     _p(add_mask), C.byref(desc), dt_code(q.dtype), _stream()), "attn_fwd")
     return stat_m, stat_l
 
@@ -299,12 +299,8 @@ def attn_fwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, desc: AttnDesc, slope
 def attn_bwd(q, k, v, o, d_o, stat_m, stat_l, dq, dk, dv, desc: AttnDesc, slopes, mask: Optional[MaskInfo],
              add_mask: Optional[Tensor] = None):
     delta = torch.empty((desc.B, desc.nh, desc.Sq), dtype=torch.float32, device=q.device)
-    check(_lib.load().ctmi_attn_bwd(_view_ptr(q), _view_ptr(k), _view_ptr(v), _view_ptr(o), _view_ptr(d_o), _p(stat_m), _p(stat_l),
-                                    _view_ptr(dq), _view_ptr(dk), _view_ptr(dv), _p(delta), _p(slopes),
-                                    _p(mask.kpos) if (mask is not None and slopes is not None) else None,
-                                    _p(mask.kvalid) if mask is not None else None,
-                                    _p(mask.first_valid) if mask is not None else None,
-                                    _p(add_mask), C.byref(desc), dt_code(q.dtype), _stream()), "attn_bwd")
+    check(_lib.load().ctmi_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(d_o), _p(stat_m), _p(stat_l), _p(dq), _p(dk), _p(dv), _p(delta), _p(slopes),
+                                    *MaskInfo.ptrs(mask, slopes), _p(add_mask), C.byref(desc), dt_code(q.dtype), _stream()), "attn_bwd")
 
 
 def fused_qkv_desc(B: int, S: int, nh: int, hd: int, causal: bool, dropout_p: float = 0.0, dropout_seed: int = 0) -> AttnDesc:
@@ -681,9 +677,7 @@ def _fill_block_desc(d: "_lib.BloomBlock", x2: Tensor, params, mask: Optional[Ma
     for name, t in zip(_lib.BLK_PARAMS, params):
         setattr(d, name, t.data_ptr())
     d.slopes = None if slopes is None else slopes.data_ptr()
-    d.kpos = mask.kpos.data_ptr() if (mask is not None and slopes is not None) else None
-    d.kvalid = None if mask is None else mask.kvalid.data_ptr()
-    d.first_valid = None if mask is None else mask.first_valid.data_ptr()
+    d.kpos, d.kvalid, d.first_valid = MaskInfo.ptrs(mask, slopes)
     d.x = x2.data_ptr()
     d.slab = slab.data_ptr()
 

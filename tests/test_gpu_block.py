@@ -329,6 +329,14 @@ def test_block_gpt2_spelling_with_in_out_weights(dtype, B, S, H, nh):
             assert relerr(a, b) < rt and relerr(a, c) < rt, n
         if n in ("wqkv", "wd", "w1", "w2"):
             assert a.shape == p_io[names.index(n)].shape, n                                      # [in, out], the parameter's layout
+    # one stream or two: same bits, as for the Bloom spelling
+    sides = {}
+    for side in (False, True):
+        sides[side] = o.bloom_block_bwd(a_io, x, p_io, mask, None, eps, False, dout, use_side_stream=side)
+        torch.cuda.synchronize()
+    assert torch.equal(sides[False][0], sides[True][0])
+    for n, a, b in zip(names, sides[False][1], sides[True][1]):
+        assert torch.equal(a, b), n
     # [in,out] weights with [out,in] gradients (the fourth flag combination): the same numbers, transposed
     a_x = o.bloom_block_fwd(x, p_io, mask, None, eps, False, B, S, nh, flags=L.BLK_QKV_BLOCKED | L.BLK_W_IN_OUT, attn_scale=scale, future_fill=-1e4)
     dx_x, g_x = o.bloom_block_bwd(a_x, x, p_io, mask, None, eps, False, dout)
