@@ -961,50 +961,58 @@ static void launch_k(K kern, int64_t grid, size_t lds, hipStream_t st, AttnP& p)
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, p);
 }
 
+// The five (AM, FAST, DROP) instantiations every kernel family has: f(AM, FAST, DROP) as bool constants, for the one that fits the call
+// (dropout: general kernels only — not the measured path; FAST: no additive mask, 16-byte rows, hd == HDP).
+template <typename F>
+static void attn_variant(const AttnP& p, int hdp, F&& f) {
+    constexpr std::true_type Y{}; constexpr std::false_type N{};
+    if (p.drop_thr != 0) { if (p.add_mask) f(Y, N, Y); else f(N, N, Y); }
+    else if (p.add_mask) f(Y, N, N);
+    else if (p.vec_ok && p.hd == hdp) f(N, Y, N);
+    else f(N, N, N);
+}
+#define ATTN_VARIANT_OF(KERNEL) &KERNEL<T, HDP, decltype(am)::value, decltype(fast)::value, decltype(drop)::value>
+
 template <typename T, int HDP>
 static int fwd_launch(AttnP& p, hipStream_t st) {
-    using A = AT<T, HDP>;
     const size_t lds = (size_t)FwdStage<T, HDP>::BYTES * nbuf_for(FwdStage<T, HDP>::BYTES);
     const int64_t grid = ((p.Sq + 63) / 64) * p.B * p.nh;
-    if (p.drop_thr != 0) {                                             // dropout instantiations: general kernels only (not the measured path)
-            if (p.add_mask) launch_k(&attn_fwd_kernel<T, HDP, true, false, true>, grid, lds, st, p);
-            else launch_k(&attn_fwd_kernel<T, HDP, false, false, true>, grid, lds, st, p);
-        } else if (p.add_mask) launch_k(&attn_fwd_kernel<T, HDP, true, false>, grid, lds, st, p);
-        else if (p.vec_ok && p.hd == HDP) launch_k(&attn_fwd_kernel<T, HDP, false, true>, grid, lds, st, p);
-        else launch_k(&attn_fwd_kernel<T, HDP, false, false>, grid, lds, st, p);
+    attn_variant(p, HDP, [&](auto am, auto fast, auto drop) { launch_k(ATTN_VARIANT_OF(attn_fwd_kernel), grid, lds, st, p); });
     CTMI_CHECK_LAUNCH("attn_fwd");
     return CTMI_OK;
 }
 template <typename T, int HDP>
 static int bwd_launch(AttnP& p, hipStream_t st) {
-    using A = AT<T, HDP>;
     {   // dQ first: it also publishes delta = rowsum(dO * O) for the dK/dV kernel below (same stream: ordered)
         const size_t lds = (size_t)DqStage<T, HDP>::BYTES * nbuf_for(DqStage<T, HDP>::BYTES);
         const int64_t grid = ((p.Sq + 63) / 64) * p.B * p.nh;
-        if (p.drop_thr != 0) {                                             // dropout instantiations: general kernels only (not the measured path)
-            if (p.add_mask) launch_k(&attn_bwd_dq_kernel<T, HDP, true, false, true>, grid, lds, st, p);
-            else launch_k(&attn_bwd_dq_kernel<T, HDP, false, false, true>, grid, lds, st, p);
-        } else if (p.add_mask) launch_k(&attn_bwd_dq_kernel<T, HDP, true, false>, grid, lds, st, p);
-        else if (p.vec_ok && p.hd == HDP) launch_k(&attn_bwd_dq_kernel<T, HDP, false, true>, grid, lds, st, p);
-        else launch_k(&attn_bwd_dq_kernel<T, HDP, false, false>, grid, lds, st, p);
+        attn_variant(p, HDP, [&](auto am, auto fast, auto drop) { launch_k(ATTN_VARIANT_OF(attn_bwd_dq_kernel), grid, lds, st, p); });
         CTMI_CHECK_LAUNCH("attn_bwd_dq");
     }
     {
         const size_t lds = (size_t)DkdvStage<T, HDP>::BYTES * nbuf_for(DkdvStage<T, HDP>::BYTES);
         const int64_t grid = ((p.Sk + 63) / 64) * p.B * p.nh;
-        if (p.drop_thr != 0) {                                             // dropout instantiations: general kernels only (not the measured path)
-            if (p.add_mask) launch_k(&attn_bwd_dkdv_kernel<T, HDP, true, false, true>, grid, lds, st, p);
-            else launch_k(&attn_bwd_dkdv_kernel<T, HDP, false, false, true>, grid, lds, st, p);
-        } else if (p.add_mask) launch_k(&attn_bwd_dkdv_kernel<T, HDP, true, false>, grid, lds, st, p);
-        else if (p.vec_ok && p.hd == HDP) launch_k(&attn_bwd_dkdv_kernel<T, HDP, false, true>, grid, lds, st, p);
-        else launch_k(&attn_bwd_dkdv_kernel<T, HDP, false, false>, grid, lds, st, p);
+        attn_variant(p, HDP, [&](auto am, auto fast, auto drop) { launch_k(ATTN_VARIANT_OF(attn_bwd_dkdv_kernel), grid, lds, st, p); });
         CTMI_CHECK_LAUNCH("attn_bwd_dkdv");
     }
     return CTMI_OK;
 }
+#undef ATTN_VARIANT_OF
 
-#define HDP_DISPATCH(FN, T) \
-    (p.hd <= 32 ? FN<T, 32>(p, st) : (p.hd <= 64 ? FN<T, 64>(p, st) : FN<T, 128>(p, st)))
+// bf16 / fp16 training shapes take the 128-row kernels (attention_w32.hip), which say whether the problem is theirs; everything else — and fp32
+// always — the general kernels, by head-dim class.  (fill_params has already refused any other dtype code.)
+template <bool BWD>
+static int attn_run(AttnP& p, int dtype, hipStream_t st) {
+    if (dtype != CTMI_F32 && (BWD ? ctmi_attn32_bwd(p, st, dtype == CTMI_F16) : ctmi_attn32_fwd(p, st, dtype == CTMI_F16))) {
+        CTMI_CHECK_LAUNCH(BWD ? "attn32_bwd" : "attn32_fwd");
+        return CTMI_OK;
+    }
+    return ctmi_by_dtype(dtype, BWD ? "attn_bwd" : "attn_fwd", [&](auto t) -> int {
+        using T = decltype(t);
+        if constexpr (BWD) return p.hd <= 32 ? bwd_launch<T, 32>(p, st) : (p.hd <= 64 ? bwd_launch<T, 64>(p, st) : bwd_launch<T, 128>(p, st));
+        else               return p.hd <= 32 ? fwd_launch<T, 32>(p, st) : (p.hd <= 64 ? fwd_launch<T, 64>(p, st) : fwd_launch<T, 128>(p, st));
+    });
+}
 
 extern "C" int ctmi_attn_fwd(const void* q, const void* k, const void* v, void* o, float* stat_m, float* stat_l,
                              const float* slopes, const float* kpos, const int32_t* kvalid, const int32_t* first_valid,
@@ -1019,13 +1027,7 @@ extern "C" int ctmi_attn_fwd(const void* q, const void* k, const void* v, void* 
     if (rc != CTMI_OK) return rc;
     hipStream_t st = as_stream(stream);
     ProfScope prof__(CTMI_PROF_ATTN_FWD, st);
-    if (dtype == CTMI_F32) return HDP_DISPATCH(fwd_launch, float);
-    if (dtype == CTMI_F16) {                                                             // fp16: the same two kernel families
-        if (ctmi_attn32_fwd(p, st, 1)) { CTMI_CHECK_LAUNCH("attn32_fwd"); return CTMI_OK; }
-        return HDP_DISPATCH(fwd_launch, f16_t);
-    }
-    if (ctmi_attn32_fwd(p, st)) { CTMI_CHECK_LAUNCH("attn32_fwd"); return CTMI_OK; }   // training shapes: attention_w32.hip
-    return HDP_DISPATCH(fwd_launch, bf16_t);
+    return attn_run<false>(p, dtype, st);
 }
 
 extern "C" int ctmi_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o,
@@ -1043,11 +1045,5 @@ extern "C" int ctmi_attn_bwd(const void* q, const void* k, const void* v, const 
     if (rc != CTMI_OK) return rc;
     hipStream_t st = as_stream(stream);
     ProfScope prof__(CTMI_PROF_ATTN_BWD, st);
-    if (dtype == CTMI_F32) return HDP_DISPATCH(bwd_launch, float);
-    if (dtype == CTMI_F16) {
-        if (ctmi_attn32_bwd(p, st, 1)) { CTMI_CHECK_LAUNCH("attn32_bwd"); return CTMI_OK; }
-        return HDP_DISPATCH(bwd_launch, f16_t);
-    }
-    if (ctmi_attn32_bwd(p, st)) { CTMI_CHECK_LAUNCH("attn32_bwd"); return CTMI_OK; }   // training shapes: attention_w32.hip
-    return HDP_DISPATCH(bwd_launch, bf16_t);
+    return attn_run<true>(p, dtype, st);
 }

@@ -886,21 +886,10 @@ int ctmi_attn32_fwd(const AttnP& p, hipStream_t st, int f16) {
     constexpr int NW = CTMI_W32_FWD_NW, RPB = 32 * NW;
     const bool replace = p.future_fill > FINFO_MIN;
     const int64_t grid = ((p.Sq + RPB - 1) / RPB) * BH;
-    if (f16) {
-        if (p.hd == 64) {
-            if (replace) launch32(&attn32_fwd_kernel<64, NW, true, true>, grid, 64 * NW, lds_kv<64, NW>(p, CTMI_W32_FWD_NST), st, p);
-            else launch32(&attn32_fwd_kernel<64, NW, false, true>, grid, 64 * NW, lds_kv<64, NW>(p, CTMI_W32_FWD_NST), st, p);
-        } else {
-            if (replace) launch32(&attn32_fwd_kernel<128, NW, true, true>, grid, 64 * NW, lds_kv<128, NW>(p, CTMI_W32_FWD_NST), st, p);
-            else launch32(&attn32_fwd_kernel<128, NW, false, true>, grid, 64 * NW, lds_kv<128, NW>(p, CTMI_W32_FWD_NST), st, p);
-        }
-    } else if (p.hd == 64) {
-        if (replace) launch32(&attn32_fwd_kernel<64, NW, true>, grid, 64 * NW, lds_kv<64, NW>(p, CTMI_W32_FWD_NST), st, p);
-        else launch32(&attn32_fwd_kernel<64, NW, false>, grid, 64 * NW, lds_kv<64, NW>(p, CTMI_W32_FWD_NST), st, p);
-    } else {
-        if (replace) launch32(&attn32_fwd_kernel<128, NW, true>, grid, 64 * NW, lds_kv<128, NW>(p, CTMI_W32_FWD_NST), st, p);
-        else launch32(&attn32_fwd_kernel<128, NW, false>, grid, 64 * NW, lds_kv<128, NW>(p, CTMI_W32_FWD_NST), st, p);
-    }
+    ctmi_by_flags([&](auto f16c, auto hd64, auto rep) {
+        constexpr int HD = decltype(hd64)::value ? 64 : 128;
+        launch32(&attn32_fwd_kernel<HD, NW, decltype(rep)::value, decltype(f16c)::value>, grid, 64 * NW, lds_kv<HD, NW>(p, CTMI_W32_FWD_NST), st, p);
+    }, f16 != 0, p.hd == 64, replace);
     return 1;
 }
 
@@ -914,25 +903,15 @@ int ctmi_attn32_bwd(const AttnP& p, hipStream_t st, int f16) {
     const int64_t BH = p.B * p.nh;
     // dQ first: it also publishes delta = rowsum(dO * O) for the dK/dV kernel (same stream: ordered)
     constexpr int NW = CTMI_W32_BWD_NW, RPB = 32 * NW, NST = CTMI_W32_BWD_NST;
-    if (p.hd == 128) {                                                           // round 5: dQ, then dV and dK in two passes (see MODE)
-        const int64_t gq = ((p.Sq + RPB - 1) / RPB) * BH, gk = ((p.Sk + RPB - 1) / RPB) * BH;
-        if (f16) {
-            launch32(&attn32_dq_kernel<128, NW, true>, gq, 64 * NW, lds_kv<128, NW>(p, NST), st, p);
-            launch32(&attn32_dkdv_kernel<128, NW, true, 1>, gk, 64 * NW, lds_qg<128, NW>(p, NST, 1), st, p);
-            launch32(&attn32_dkdv_kernel<128, NW, true, 2>, gk, 64 * NW, lds_qg<128, NW>(p, NST), st, p);
-        } else {
-            launch32(&attn32_dq_kernel<128, NW, false>, gq, 64 * NW, lds_kv<128, NW>(p, NST), st, p);
-            launch32(&attn32_dkdv_kernel<128, NW, false, 1>, gk, 64 * NW, lds_qg<128, NW>(p, NST, 1), st, p);
-            launch32(&attn32_dkdv_kernel<128, NW, false, 2>, gk, 64 * NW, lds_qg<128, NW>(p, NST), st, p);
-        }
-        return 1;
-    }
-    if (f16) {
-        launch32(&attn32_dq_kernel<64, NW, true>, ((p.Sq + RPB - 1) / RPB) * BH, 64 * NW, lds_kv<64, NW>(p, NST), st, p);
-        launch32(&attn32_dkdv_kernel<64, NW, true>, ((p.Sk + RPB - 1) / RPB) * BH, 64 * NW, lds_qg<64, NW>(p, NST), st, p);
-        return 1;
-    }
-    launch32(&attn32_dq_kernel<64, NW>, ((p.Sq + RPB - 1) / RPB) * BH, 64 * NW, lds_kv<64, NW>(p, NST), st, p);
-    launch32(&attn32_dkdv_kernel<64, NW>, ((p.Sk + RPB - 1) / RPB) * BH, 64 * NW, lds_qg<64, NW>(p, NST), st, p);
+    const int64_t gq = ((p.Sq + RPB - 1) / RPB) * BH, gk = ((p.Sk + RPB - 1) / RPB) * BH;
+    ctmi_by_flags([&](auto f16c, auto hd64) {
+        constexpr bool F16 = decltype(f16c)::value;
+        constexpr int HD = decltype(hd64)::value ? 64 : 128;
+        launch32(&attn32_dq_kernel<HD, NW, F16>, gq, 64 * NW, lds_kv<HD, NW>(p, NST), st, p);
+        if constexpr (HD == 128) {                                               // round 5: dV and dK in two passes (see MODE)
+            launch32(&attn32_dkdv_kernel<HD, NW, F16, 1>, gk, 64 * NW, lds_qg<HD, NW>(p, NST, 1), st, p);
+            launch32(&attn32_dkdv_kernel<HD, NW, F16, 2>, gk, 64 * NW, lds_qg<HD, NW>(p, NST), st, p);
+        } else launch32(&attn32_dkdv_kernel<HD, NW, F16>, gk, 64 * NW, lds_qg<HD, NW>(p, NST), st, p);
+    }, f16 != 0, p.hd == 64);
     return 1;
 }

@@ -1,7 +1,7 @@
 // One Bloom block per call: the launch sequences of modeling_bloom.py:142-159 (forward) and of its hand-derived
 // backward, issued from C++ so that the Python host makes ONE call per block and direction instead of 7 / 17+ kernel-level
 // calls (the round-1 profile had the host enqueue at 26-35 ms per 43 ms step — above the target step time).
-// Host-side orchestration only: every arithmetic step is one of the kernels in gemm.hip / attention.hip / elementwise.hip.
+// Host-side orchestration only: every arithmetic step is one of the kernels in gemm.hip / attention.hip / layernorm.hip / elementwise.hip.
 //
 // Backward, round 5 (bf16, aligned geometry; CTMI_WGRAD_GROUP != 0): the data-gradient chain below runs on the main stream unchanged; the FOUR
 // weight gradients and the column sums of du / dqkv (db1, dbqkv) are ONE grouped launch on the side stream (ctmi_wgrad_grouped, csrc/gemm.hip),

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <stdarg.h>
+#include <type_traits>
 #include "../../include/ctmi355.h"
 
 typedef uint16_t bf16_t;                                   // raw bfloat16 bits
@@ -132,6 +133,27 @@ __device__ __forceinline__ void st_wt8(void* p, const uint2& v) {
 #endif
 }
 
+// ---------------------------------------------------------------- streaming (non-temporal) 16-byte accesses
+// For single-pass kernels whose data is far larger than the 256 MiB Infinity Cache (the optimizer walks 16.8 GB per step, the loss backward
+// 8.2 GB): no line is ever reused, so none should be kept.
+typedef float f32x4_nt __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4_nt __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ldg_stream(const float* p) {
+    const f32x4_nt v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt*>(p));
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ void stg_stream(float* p, const float4& v) {
+    __builtin_nontemporal_store(f32x4_nt{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4_nt*>(p));
+}
+
+__device__ __forceinline__ uint4 ldg_stream16(const void* p) {
+    const u32x4_nt v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_nt*>(p));
+    return make_uint4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ void stg_stream16(void* p, const uint4& v) {
+    __builtin_nontemporal_store(u32x4_nt{v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4_nt*>(p));
+}
+
 // ---------------------------------------------------------------- wave / block reductions
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -190,3 +212,28 @@ static inline uint32_t ctmi_drop_threshold(float p) {                  // p in [
 static inline int ctmi_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// ---------------------------------------------------------------- dtype dispatch (host)
+// A storage-type code to a C++ type, once per entry: f(T{}) with T = float | bf16_t | f16_t, so the launch line of an entry is written once
+// (`using T = decltype(t)`, 16 / sizeof(T) elements per 16-byte vector).  Any other code: "<who>: unsupported dtype %d", CTMI_ERR_UNSUPPORTED.
+template <typename F> static inline int ctmi_by_dtype(int dtype, const char* who, F&& f) {
+    if (dtype == CTMI_F32) return f(float{});
+    if (dtype == CTMI_BF16) return f(bf16_t{});
+    if (dtype == CTMI_F16) return f(f16_t{});
+    ctmi_set_error("%s: unsupported dtype %d", who, dtype);
+    return CTMI_ERR_UNSUPPORTED;
+}
+// the 16-bit types only (kernel families that have no fp32 form must not gain one)
+template <typename F> static inline int ctmi_by_dtype16(int dtype, const char* who, F&& f) {
+    if (dtype == CTMI_BF16) return f(bf16_t{});
+    if (dtype == CTMI_F16) return f(f16_t{});
+    ctmi_set_error("%s: unsupported dtype %d", who, dtype);
+    return CTMI_ERR_UNSUPPORTED;
+}
+// run-time flags to template constants: f(std::bool_constant<flag>{}...), one call for the one combination that holds
+template <typename F> static inline void ctmi_by_flags(F&& f) { f(); }
+template <typename F, typename... B> static inline void ctmi_by_flags(F&& f, bool flag, B... rest) {
+    if (flag) ctmi_by_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else      ctmi_by_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}

@@ -222,8 +222,6 @@ __global__ __launch_bounds__(256) void lora_wgrad_reduce_k(const float* __restri
     out[(e / Q) * ldo + (e % Q)] = alpha * v;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 #define LORA_UNSUPPORTED(cond, ...) do { if (!(cond)) { ctmi_set_error(__VA_ARGS__); return CTMI_ERR_UNSUPPORTED; } } while (0)
 
 void wgrad_plan(int64_t T, int64_t P, int64_t Q, int* splits, int* chunk) {
@@ -257,6 +255,11 @@ void launch_expand(const void* xa, int64_t ldxa, const void* w, int64_t ldw, voi
     else         hipLaunchKernelGGL((lora_expand_add_k<T, 2, KM>), grid, block, 0, st, X, ldxa, W, ldw, Y, ldy, Trows, N, r);
 }
 
+// the (bf16 | fp16) x (W row-major | k-major) choice of project and expand-add: f(T{}, bool constant KMAJOR)
+template <typename F> int by_dtype_layout(int dtype, int w_kmajor, const char* who, F&& f) {
+    return ctmi_by_dtype16(dtype, who, [&](auto t) -> int { return w_kmajor ? f(t, std::true_type{}) : f(t, std::false_type{}); });
+}
+
 }  // namespace
 
 extern "C" int ctmi_lora_project(const void* x, int64_t ldx, const void* w, int64_t ldw, int w_kmajor, void* out, int64_t ldo,
@@ -268,10 +271,11 @@ extern "C" int ctmi_lora_project(const void* x, int64_t ldx, const void* w, int6
                      "lora_project: leading dimensions %lld / %lld / %lld (multiples of 8, at least the row length)", (long long)ldx, (long long)ldw, (long long)ldo);
     LORA_UNSUPPORTED(x && w && out && aligned16(x) && aligned16(w), "lora_project: NULL or unaligned pointer (16 bytes)");
     hipStream_t st = as_stream(stream);
-    if (dtype == CTMI_BF16) { if (w_kmajor) launch_project<bf16_t, true>(x, ldx, w, ldw, out, ldo, T, (int)K, (int)r, alpha, st); else launch_project<bf16_t, false>(x, ldx, w, ldw, out, ldo, T, (int)K, (int)r, alpha, st); }
-    else                    { if (w_kmajor) launch_project<f16_t, true>(x, ldx, w, ldw, out, ldo, T, (int)K, (int)r, alpha, st);  else launch_project<f16_t, false>(x, ldx, w, ldw, out, ldo, T, (int)K, (int)r, alpha, st); }
-    CTMI_CHECK_LAUNCH("lora_project");
-    return CTMI_OK;
+    return by_dtype_layout(dtype, w_kmajor, "lora_project", [&](auto t, auto km) -> int {
+        launch_project<decltype(t), decltype(km)::value>(x, ldx, w, ldw, out, ldo, T, (int)K, (int)r, alpha, st);
+        CTMI_CHECK_LAUNCH("lora_project");
+        return CTMI_OK;
+    });
 }
 
 extern "C" int ctmi_lora_expand_add(const void* xa, int64_t ldxa, const void* w, int64_t ldw, int w_kmajor, void* y, int64_t ldy,
@@ -283,10 +287,11 @@ extern "C" int ctmi_lora_expand_add(const void* xa, int64_t ldxa, const void* w,
                      "lora_expand_add: leading dimensions %lld / %lld / %lld (multiples of 8, at least the row length)", (long long)ldxa, (long long)ldw, (long long)ldy);
     LORA_UNSUPPORTED(xa && w && y && aligned16(xa) && aligned16(w) && aligned16(y), "lora_expand_add: NULL or unaligned pointer (16 bytes)");
     hipStream_t st = as_stream(stream);
-    if (dtype == CTMI_BF16) { if (w_kmajor) launch_expand<bf16_t, true>(xa, ldxa, w, ldw, y, ldy, T, (int)N, (int)r, st); else launch_expand<bf16_t, false>(xa, ldxa, w, ldw, y, ldy, T, (int)N, (int)r, st); }
-    else                    { if (w_kmajor) launch_expand<f16_t, true>(xa, ldxa, w, ldw, y, ldy, T, (int)N, (int)r, st);  else launch_expand<f16_t, false>(xa, ldxa, w, ldw, y, ldy, T, (int)N, (int)r, st); }
-    CTMI_CHECK_LAUNCH("lora_expand_add");
-    return CTMI_OK;
+    return by_dtype_layout(dtype, w_kmajor, "lora_expand_add", [&](auto t, auto km) -> int {
+        launch_expand<decltype(t), decltype(km)::value>(xa, ldxa, w, ldw, y, ldy, T, (int)N, (int)r, st);
+        CTMI_CHECK_LAUNCH("lora_expand_add");
+        return CTMI_OK;
+    });
 }
 
 extern "C" int64_t ctmi_lora_wgrad_ws(int64_t T, int64_t P, int64_t Q) {
@@ -311,9 +316,13 @@ extern "C" int ctmi_lora_wgrad(const void* l, int64_t ldl, const void* r, int64_
     hipStream_t st = as_stream(stream);
     const int qtiles = (int)cdiv64(Q, 64);
     const dim3 grid((unsigned)(cdiv64(P, 64) * qtiles), (unsigned)splits), block(256);
-    if (dtype == CTMI_BF16) hipLaunchKernelGGL((lora_wgrad_k<bf16_t>), grid, block, 0, st, (const bf16_t*)l, ldl, (const bf16_t*)r, ldr, ws, T, (int)P, (int)Q, qtiles, chunk);
-    else                    hipLaunchKernelGGL((lora_wgrad_k<f16_t>), grid, block, 0, st, (const f16_t*)l, ldl, (const f16_t*)r, ldr, ws, T, (int)P, (int)Q, qtiles, chunk);
-    CTMI_CHECK_LAUNCH("lora_wgrad");
+    const int rc = ctmi_by_dtype16(dtype, "lora_wgrad", [&](auto t) -> int {
+        using TT = decltype(t);
+        hipLaunchKernelGGL((lora_wgrad_k<TT>), grid, block, 0, st, (const TT*)l, ldl, (const TT*)r, ldr, ws, T, (int)P, (int)Q, qtiles, chunk);
+        CTMI_CHECK_LAUNCH("lora_wgrad");
+        return CTMI_OK;
+    });
+    if (rc != CTMI_OK) return rc;
     hipLaunchKernelGGL(lora_wgrad_reduce_k, dim3((unsigned)cdiv64(P * Q, 256)), block, 0, st, ws, out, ldo, (int)P, (int)Q, splits, alpha);
     CTMI_CHECK_LAUNCH("lora_wgrad_reduce");
     return CTMI_OK;

@@ -1,5 +1,5 @@
-// The multi-job partial-row reduction of a transformer block's backward (see elementwise.hip: ctmi_reduce_jobs), as a device function two kernels
-// share: reduce_jobs_k (elementwise.hip) and wgrad_tail_k (gemm.hip: the same jobs in ONE launch with the sum of the K-halves of a grouped
+// The multi-job partial-row reduction of a transformer block's backward (see layernorm.hip: ctmi_reduce_jobs), as a device function two kernels
+// share: reduce_jobs_k (layernorm.hip) and wgrad_tail_k (gemm.hip: the same jobs in ONE launch with the sum of the K-halves of a grouped
 // weight-gradient call — round 6: one dependent launch per block less).
 #pragma once
 #include "common.h"
