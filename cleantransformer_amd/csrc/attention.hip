@@ -14,52 +14,12 @@
 #include "mma.h"
 #include <type_traits>
 
-// A/B knobs for tools/ variant builds (defaults = the adopted configuration)
-#ifndef CTMI_ATTN_SADDR
-#define CTMI_ATTN_SADDR 1        // FAST kernels: stream the K/V tiles through a scalar tile origin + constant per-lane offsets (same-box A/B: forward 281 -> 285-289 TF/s, backward 267 -> 272)
-#endif
-#ifndef CTMI_ATTN_SADDR_DKDV
-#define CTMI_ATTN_SADDR_DKDV 0
-#endif
-#ifndef CTMI_ATTN_FASTBODY
-#define CTMI_ATTN_FASTBODY 1     // backward kernels: mask-free loop body for tiles that cannot contain a masked score (A/B: slower while it costs a wave per SIMD: 207 VGPRs)
-#endif
-#ifndef CTMI_ATTN_SWAPRED
-#define CTMI_ATTN_SWAPRED 1      // forward kernel: row-max across the 4 lane groups by v_permlane{16,32}_swap instead of ds_bpermute
-#endif
-#ifndef CTMI_ATTN_MINW
-#define CTMI_ATTN_MINW 2         // __launch_bounds__ minimum waves per SIMD of the three streaming kernels (register cap = 512 / MINW)
-#endif
-#ifndef CTMI_ATTN_NBUF
-#define CTMI_ATTN_NBUF 0         // 0: two LDS stages whenever they fit (one barrier per tile); 1: force one stage (more workgroups per CU)
-#endif
-
-#ifndef CTMI_ATTN_DBG_BUILD
-#define CTMI_ATTN_DBG_BUILD 0    // 1: timing-ablation switches driven by CTMI_ATTN_DBG exist (A/B builds only); 0: compiled out
-#endif
-#if CTMI_ATTN_DBG_BUILD
-#define ATTN_DBG(p) ((p).dbg)
-#else
-#define ATTN_DBG(p) 0
-#endif
 #include "attn_params.h"
 #include "prof.h"
 
 // 64 x HDP tile staging helpers (256 threads).  Thread -> (row = id / CPR, 16-byte chunk = id % CPR): the CPR lanes of
 // one row read one contiguous run of HBM (coalesced: a head row of hd=64 bf16 is exactly one 128-byte line) and write one
 // padded row-major LDS row (pitch HDP + 8 elements: ds_write_b128 / ds_read_b128 / ds_read_b64_tr_b16 all spread over banks).
-// 16 bytes of tile data in flight: a first-class vector, NOT the uint4 struct — struct copies become memcpy intrinsics that
-// SROA left in private memory (scratch stores + vmcnt(0) after every tile load) once the scalar gather path was compiled out
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// Loads through pointers that hipcc cannot prove to be global (loop-carried / selected pointers derived from the by-value
-// kernel-argument struct) are emitted as flat_load, and a FLAT access counts on LGKM_CNT as well as VM_CNT: every
-// `s_waitcnt lgkmcnt(0)` in front of an MFMA (placed there for the LDS fragment reads) then also waited for the tile prefetch
-// issued just before it — the software pipeline was serialised on HBM/L2 latency in all three kernels.  These helpers cast to
-// the global address space explicitly, so the loads are global_load_* and only the vmcnt wait at their use sees them.
-template <typename V> __device__ __forceinline__ V ldg_as1(const void* p) {
-    typedef const __attribute__((address_space(1))) V* gptr;
-    return *(gptr)(p);
-}
 template <typename T, int HDP>
 struct AT {
     static constexpr int VEC = 16 / sizeof(T);
@@ -140,7 +100,7 @@ struct AT {
 #pragma unroll
         for (int i = 0; i < NCH; ++i) ptrs[i] += 64 * rs;
     }
-    // Offset form of the same stream (CTMI_ATTN_SADDR): the tile origin is wave-uniform, so it lives in SGPRs (advanced by scalar
+    // Offset form of the same stream (the FAST forward and dQ kernels): the tile origin is wave-uniform, so it lives in SGPRs (advanced by scalar
     // adds) and each lane keeps only a constant 32-bit byte offset — the loads become `global_load_dwordx4 v, v_off, s[base:base+1]`
     // and the NCH 64-bit VALU pointer bumps (+ the pointer copies hipcc made in front of every load) per tile and operand disappear.
     static __device__ __forceinline__ void stream_init_off(uint32_t (&offs)[NCH], int64_t rs, int tid) {
@@ -248,11 +208,6 @@ __device__ __forceinline__ void dot_tile(f32x4 (&x)[4], const T* __restrict__ rm
 // [64][HDP] LDS image (the same one dot_tile reads): the operand that must be contracted over the streamed dimension
 // (V, K, Q, dO) is fetched with ds_read_b64_tr_b16 — lane i of a 16-lane group addresses row R0 + (i>>2), columns
 // C0 + 4*(i&3).. and receives column C0 + i for rows R0..R0+3 (probe-verified) — so no transposed copy is ever staged.
-typedef short short4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 lds_tr_b16(const void* p) {
-    typedef __attribute__((address_space(3))) short4_t lds_v4;
-    return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(unsigned)(size_t)p));
-}
 template <typename T, int HDP>
 __device__ __forceinline__ void contract64(f32x4 (&acc)[HDP / 16], const T* __restrict__ rm_tile, const f32x4 (&x)[4], int lane) {
     constexpr int PRM = AT<T, HDP>::PRM;
@@ -266,8 +221,8 @@ __device__ __forceinline__ void contract64(f32x4 (&acc)[HDP / 16], const T* __re
             const T* base = rm_tile + (ks * 32 + g * 4 + (li >> 2)) * PRM + 4 * (li & 3);
 #pragma unroll
             for (int dt = 0; dt < HDP / 16; ++dt) {
-                const uint2 a0 = lds_tr_b16(base + dt * 16);                     // rows ks*32 + g*4 .. +3
-                const uint2 a1 = lds_tr_b16(base + 16 * PRM + dt * 16);          // rows ks*32 + 16 + g*4 .. +3
+                const uint2 a0 = lds_read_tr_b16(base + dt * 16);                     // rows ks*32 + g*4 .. +3
+                const uint2 a1 = lds_read_tr_b16(base + 16 * PRM + dt * 16);          // rows ks*32 + 16 + g*4 .. +3
                 const short8 a = __builtin_bit_cast(short8, make_uint4(a0.x, a0.y, a1.x, a1.y));
                 acc[dt] = Mma<T>::mma(a, b, acc[dt]);
             }
@@ -294,43 +249,26 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     return (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (bid >> 3);
 }
 
-// 3-input max in ONE instruction.  (fmaxf on MFMA results makes hipcc insert a canonicalising v_max x,x per operand.)
-__device__ __forceinline__ float max3f(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
 // max over the 4 lane groups (lanes l, l^16, l^32, l^48) of a per-lane value, without the LDS crossbar: v_permlane16_swap
 // exchanges the odd 16-lane rows of its first operand with the even rows of its second, v_permlane32_swap the upper 32 lanes of
 // the first with the lower 32 of the second; applied to two copies of v, max(a, b) is the xor-16 / xor-32 butterfly step.
 // (__shfl_xor compiles to ds_bpermute_b32: ~6 integer VALU instructions for the lane index — recomputed every tile — plus an
 // LDS round trip and an lgkmcnt(0) in the middle of the softmax dependency chain, twice per tile.)
 __device__ __forceinline__ float group_max4(float v) {
-#if CTMI_ATTN_SWAPRED
     float a = v, b = v;
     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
     float c = max3f(a, a, b), d = c;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(c), "+v"(d));
     return max3f(c, c, d);
-#else
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-#endif
 }
 
 // sum over the 4 lane groups, same idiom
 __device__ __forceinline__ float group_sum4(float v) {
-#if CTMI_ATTN_SWAPRED
     float a = v, b = v;
     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
     float c = a + b, d = c;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(c), "+v"(d));
     return c + d;
-#else
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-#endif
 }
 // dot product of two operand fragments (the lane's KL consecutive head-dim elements of two rows)
 template <typename T> __device__ __forceinline__ float frag_dot(short8 a, short8 b) {
@@ -405,10 +343,11 @@ __device__ __forceinline__ void store_own_row(T* rowp, const f32x4 (&acc)[HDP / 
 template <typename T, int HDP> struct FwdStage { static constexpr int BYTES = 2 * AT<T, HDP>::RM_ELEMS * (int)sizeof(T) + 256; };
 template <typename T, int HDP> struct DkdvStage { static constexpr int BYTES = 2 * AT<T, HDP>::RM_ELEMS * (int)sizeof(T) + 768; };
 template <typename T, int HDP> struct DqStage { static constexpr int BYTES = 2 * AT<T, HDP>::RM_ELEMS * (int)sizeof(T) + 256; };
-constexpr int nbuf_for(int stage_bytes) { return CTMI_ATTN_NBUF ? CTMI_ATTN_NBUF : (2 * stage_bytes <= 80 * 1024 ? 2 : 1); }
+constexpr int nbuf_for(int stage_bytes) { return 2 * stage_bytes <= 80 * 1024 ? 2 : 1; }
+constexpr int ATTN_MINW = 2;     // __launch_bounds__ minimum waves per SIMD of the three streaming kernels (register cap = 512 / ATTN_MINW)
 
 template <typename T, int HDP, bool AM, bool FAST, bool DROP = false>
-__global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_fwd_kernel(AttnP p) {
+__global__ __launch_bounds__(256, ATTN_MINW) void attn_fwd_kernel(AttnP p) {
     using A = AT<T, HDP>;
     constexpr int MK = Mma<T>::K, KL = Mma<T>::KL, NKK = HDP / MK, NDT = HDP / 16;
     constexpr int STAGE = FwdStage<T, HDP>::BYTES, NBUF = nbuf_for(STAGE);
@@ -460,7 +399,7 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_fwd_kernel(AttnP p) 
     const T* pk[A::NCH];
     const T* pv[A::NCH];
     uint32_t ok[A::NCH], ov[A::NCH];
-    constexpr bool SADDR = CTMI_ATTN_SADDR && FAST;
+    constexpr bool SADDR = FAST;             // offset stream (same-box A/B against the pointer stream: forward 281 -> 285-289 TF/s, backward 267 -> 272)
     if constexpr (SADDR) { A::stream_init_off(ok, p.k_rs, tid); A::stream_init_off(ov, p.v_rs, tid); }
     else { A::stream_init(pk, kp, p.k_rs, 64, tid); A::stream_init(pv, vp, p.v_rs, 64, tid); }
     if (tid < 64) rkb = key_bias(p, b, tid, slope);
@@ -472,7 +411,7 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_fwd_kernel(AttnP p) 
     const float* am_base = AM ? p.add_mask + b * p.am_b + h * p.am_h : nullptr;
 
     for (int t = 0; t < ntiles; ++t) {
-        if (t + 1 < ntiles && !(ATTN_DBG(p) & 1)) {
+        if (t + 1 < ntiles) {
             if (tid < 64) kbr.load(p, b, (int64_t)(t + 1) * 64 + tid);
             if constexpr (SADDR) {
                 A::stream_load_off(rk, ok, kp, p.k_rs, (int64_t)(t + 1) * 64, p.Sk, tid);
@@ -546,14 +485,14 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_fwd_kernel(AttnP p) 
         m = m_new;
         contract64<T, HDP>(acc, VS(cur), x, lane);                          // acc[dt][r] = O^T[d][my_q]
         if (NBUF == 1) __syncthreads();
-        if (t + 1 < ntiles && !(ATTN_DBG(p) & 2)) {
+        if (t + 1 < ntiles) {
             const int nx = NBUF == 2 ? cur ^ 1 : 0;
             A::store_rm(rk, KS(nx), tid);
             A::store_rm(rv, VS(nx), tid);
             if (tid < 64) KB(nx)[tid] = kbr.value(p, (int64_t)(t + 1) * 64 + tid, slope);
             cur = nx;
         }
-        if (!(ATTN_DBG(p) & 4)) __syncthreads();
+        __syncthreads();
     }
     lsum += __shfl_xor(lsum, 16, 64);
     lsum += __shfl_xor(lsum, 32, 64);
@@ -571,7 +510,7 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_fwd_kernel(AttnP p) 
 // own rows = keys.  Per query tile: S = Q K^T and dP = dO V^T (own key in the accumulator column), P = exp(S-m)/l,
 // dS = P (dP - delta); dV^T += dO^T P, dK^T += Q^T dS  (Q, dO staged both row-major and transposed).
 template <typename T, int HDP, bool AM, bool FAST, bool DROP = false>
-__global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_bwd_dkdv_kernel(AttnP p) {
+__global__ __launch_bounds__(256, ATTN_MINW) void attn_bwd_dkdv_kernel(AttnP p) {
     using A = AT<T, HDP>;
     constexpr int MK = Mma<T>::K, KL = Mma<T>::KL, NKK = HDP / MK, NDT = HDP / 16;
     constexpr int STAGE = DkdvStage<T, HDP>::BYTES, NBUF = nbuf_for(STAGE);
@@ -641,13 +580,12 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_bwd_dkdv_kernel(Attn
     };
     const T* pq[A::NCH];
     const T* pg[A::NCH];
-    uint32_t oq[A::NCH], og[A::NCH];
-    constexpr bool SADDR = CTMI_ATTN_SADDR_DKDV && FAST;          // (off: with it hipcc allocates 170 instead of 163 VGPRs here — the third wave per SIMD)
+    // pointer stream here, not the offset stream of the forward and dQ kernels: with the offset stream hipcc allocates 170 instead of 163 VGPRs — the third wave per SIMD
     if (qt_begin < qt_end) {
         A::load(rq, qp, p.q_rs, (int64_t)qt_begin * 64, p.Sq, hd_, fast, tid);
         A::load(rg, gp, p.o_rs, (int64_t)qt_begin * 64, p.Sq, hd_, fast, tid);
-        if constexpr (SADDR) { A::stream_init_off(oq, p.q_rs, tid); A::stream_init_off(og, p.o_rs, tid); }
-        else { A::stream_init(pq, qp, p.q_rs, (int64_t)(qt_begin + 1) * 64, tid); A::stream_init(pg, gp, p.o_rs, (int64_t)(qt_begin + 1) * 64, tid); }
+        A::stream_init(pq, qp, p.q_rs, (int64_t)(qt_begin + 1) * 64, tid);
+        A::stream_init(pg, gp, p.o_rs, (int64_t)(qt_begin + 1) * 64, tid);
         load_stats(qt_begin);
         A::store_rm(rq, QS(0), tid);
         A::store_rm(rg, GS(0), tid);
@@ -660,18 +598,13 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_bwd_dkdv_kernel(Attn
     // keys still get P through their FINFO_MIN bias (uniform rows) and their dK column is zeroed once, after the loop; rows
     // q >= Sq exist only in a tile that reaches beyond Sq.  The exception is a batch row with LEFT padding: its leading queries
     // see only masked keys (uniform over ALL keys), so every tile of such a row keeps the general body.
-    const bool general = AM || !CTMI_ATTN_FASTBODY || (p.kvalid != nullptr && p.first_valid[b] - p.off > 0);
+    const bool general = AM || (p.kvalid != nullptr && p.first_valid[b] - p.off > 0);
     auto body = [&](auto masked_c, const int t) __attribute__((always_inline)) {
         constexpr bool MASKED = decltype(masked_c)::value;
-        if (t + 1 < qt_end && !(ATTN_DBG(p) & 1)) {
+        if (t + 1 < qt_end) {
             load_stats(t + 1);
-            if constexpr (SADDR) {
-                A::stream_load_off(rq, oq, qp, p.q_rs, (int64_t)(t + 1) * 64, p.Sq, tid);
-                A::stream_load_off(rg, og, gp, p.o_rs, (int64_t)(t + 1) * 64, p.Sq, tid);
-            } else {
-                A::stream_load(rq, pq, qp, p.q_rs, (int64_t)(t + 1) * 64, p.Sq, hd_, fast, tid);
-                A::stream_load(rg, pg, gp, p.o_rs, (int64_t)(t + 1) * 64, p.Sq, hd_, fast, tid);
-            }
+            A::stream_load(rq, pq, qp, p.q_rs, (int64_t)(t + 1) * 64, p.Sq, hd_, fast, tid);
+            A::stream_load(rg, pg, gp, p.o_rs, (int64_t)(t + 1) * 64, p.Sq, hd_, fast, tid);
         }
         f32x4 x[4], y[4];
         const float* st = ST(cur);
@@ -731,7 +664,7 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_bwd_dkdv_kernel(Attn
         contract64<T, HDP>(dv, GS(cur), x, lane);                            // dV^T[d][my_k] += sum_q dO[q][d] P[q][my_k]
         contract64<T, HDP>(dk, QS(cur), y, lane);                            // dK^T[d][my_k] += sum_q Q[q][d] dS[q][my_k]
         if (NBUF == 1) __syncthreads();
-        if (t + 1 < qt_end && !(ATTN_DBG(p) & 2)) {
+        if (t + 1 < qt_end) {
             const int nx = NBUF == 2 ? cur ^ 1 : 0;
             A::store_rm(rq, QS(nx), tid);
             A::store_rm(rg, GS(nx), tid);
@@ -771,7 +704,7 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_bwd_dkdv_kernel(Attn
 // ------------------------------------------------------------------------------------------------ backward: dQ
 // own rows = queries.  Per key tile: S^T = K Q^T, dP^T = V dO^T, dS^T = P^T (dP^T - delta); dQ^T += K^T dS^T.
 template <typename T, int HDP, bool AM, bool FAST, bool DROP = false>
-__global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_bwd_dq_kernel(AttnP p) {
+__global__ __launch_bounds__(256, ATTN_MINW) void attn_bwd_dq_kernel(AttnP p) {
     using A = AT<T, HDP>;
     constexpr int MK = Mma<T>::K, KL = Mma<T>::KL, NKK = HDP / MK, NDT = HDP / 16;
     constexpr int STAGE = DqStage<T, HDP>::BYTES, NBUF = nbuf_for(STAGE);
@@ -838,7 +771,7 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_bwd_dq_kernel(AttnP 
     const T* pk[A::NCH];
     const T* pv[A::NCH];
     uint32_t ok[A::NCH], ov[A::NCH];
-    constexpr bool SADDR = CTMI_ATTN_SADDR && FAST;
+    constexpr bool SADDR = FAST;             // offset stream (same-box A/B against the pointer stream: forward 281 -> 285-289 TF/s, backward 267 -> 272)
     if constexpr (SADDR) { A::stream_init_off(ok, p.k_rs, tid); A::stream_init_off(ov, p.v_rs, tid); }
     else { A::stream_init(pk, kp, p.k_rs, 64, tid); A::stream_init(pv, vp, p.v_rs, 64, tid); }
     if (tid < 64) rkb = key_bias(p, b, tid, slope);
@@ -851,10 +784,10 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_bwd_dq_kernel(AttnP 
     // padding keys carry the FINFO_MIN bias, so P — and with it dS — is exactly 0 for every row that sees a real key; that is
     // every row unless the batch row has LEFT padding (leading queries see only masked keys: P uniform, dS must still be 0) or
     // the query block reaches beyond Sq (dead rows: 1/l = 0 but exp of an un-shifted score may overflow) — those keep the general body.
-    const bool general = AM || !CTMI_ATTN_FASTBODY || (p.kvalid != nullptr && p.first_valid[b] - p.off > 0) || (q0 + 64 > p.Sq);
+    const bool general = AM || (p.kvalid != nullptr && p.first_valid[b] - p.off > 0) || (q0 + 64 > p.Sq);
     auto body = [&](auto masked_c, const int t) __attribute__((always_inline)) {
         constexpr bool MASKED = decltype(masked_c)::value;
-        if (t + 1 < ntiles && !(ATTN_DBG(p) & 1)) {
+        if (t + 1 < ntiles) {
             if (tid < 64) kbr.load(p, b, (int64_t)(t + 1) * 64 + tid);
             if constexpr (SADDR) {
                 A::stream_load_off(rk, ok, kp, p.k_rs, (int64_t)(t + 1) * 64, p.Sk, tid);
@@ -903,7 +836,7 @@ __global__ __launch_bounds__(256, CTMI_ATTN_MINW) void attn_bwd_dq_kernel(AttnP 
         }
         contract64<T, HDP>(dq, KS(cur), y, lane);                            // dQ^T[d][my_q] += sum_key K[key][d] dS[my_q][key]
         if (NBUF == 1) __syncthreads();
-        if (t + 1 < ntiles && !(ATTN_DBG(p) & 2)) {
+        if (t + 1 < ntiles) {
             const int nx = NBUF == 2 ? cur ^ 1 : 0;
             A::store_rm(rk, KS(nx), tid);
             A::store_rm(rv, VS(nx), tid);
@@ -944,7 +877,6 @@ static int fill_params(AttnP& p, const ctmi_attn_desc* d, int dtype, const char*
     p.drop_scale = 1.0f / (1.0f - d->dropout_p);
     p.future_fill = d->future_fill == 0.0f ? FINFO_MIN : d->future_fill;
     CTMI_REQUIRE(p.future_fill < 0.0f && p.future_fill >= FINFO_MIN, "%s: future_fill must be 0 (= finfo.min) or a negative finite value", who);
-    { static const int dbg = ctmi_env_int("CTMI_ATTN_DBG", 0); p.dbg = dbg; }
     const int vec = dtype == CTMI_F32 ? 4 : 8;
     auto ok = [&](const void* ptr, int64_t a, int64_t b2, int64_t c) {
         return ptr == nullptr || (((((uintptr_t)ptr) & 15) == 0) && a % vec == 0 && b2 % vec == 0 && c % vec == 0);

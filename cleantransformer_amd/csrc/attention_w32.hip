@@ -27,48 +27,18 @@
 // row statistics are published in natural units (m, l) exactly as attention.hip does, so forward / backward kernels of the
 // two files can be mixed.
 #include "common.h"
+#include "mma.h"
 #include "attn_params.h"
 #include <stdlib.h>
 #include <atomic>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8_w32 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_w32 __attribute__((ext_vector_type(8)));
-typedef short short4_w32 __attribute__((ext_vector_type(4)));
 
 // forward: 4-wave workgroups (128 query rows), three per CU at head_dim 64 (168 registers, 3 waves per SIMD from workgroups that no
 // barrier couples); K/V ring depth 2 (40 KiB of LDS per workgroup at S = 1024: three fit)
-#ifndef CTMI_W32_FWD_NW
-#define CTMI_W32_FWD_NW 4
-#endif
-#ifndef CTMI_W32_FWD_NST
-#define CTMI_W32_FWD_NST 2
-#endif
+constexpr int W32_FWD_NW = 4, W32_FWD_NST = 2;
 // backward, head_dim 64: 4-wave workgroups too — dQ three per CU (168 registers), dK/dV two per CU (256 registers)
-#ifndef CTMI_W32_BWD_NW
-#define CTMI_W32_BWD_NW 4
-#endif
-#ifndef CTMI_W32_BWD_NST
-#define CTMI_W32_BWD_NST 2
-#endif
-// forward: log2 of the growth of a row maximum that is tolerated before O / l are rescaled (0 = rescale whenever a maximum moved)
-#ifndef CTMI_W32_DEFER_MAX
-#define CTMI_W32_DEFER_MAX 0
-#endif
-// -DCTMI_W32_TIMING=1 (tools/ variant builds only): the forward kernel accumulates s_memtime deltas per wave — matrix segments,
-// vector segments, barrier waits after each — and dumps them over stat_l (which is then garbage): tools/attn_w32_timing.py
-#ifndef CTMI_W32_TIMING
-#define CTMI_W32_TIMING 0
-#endif
-#if CTMI_W32_TIMING
-#define W32_TICK(acc) do { const uint64_t now__ = __builtin_amdgcn_s_memtime(); acc += (uint32_t)(now__ - tlast); tlast = now__; } while (0)
-#else
-#define W32_TICK(acc) do { } while (0)
-#endif
-// forward: which segment raises its wave priority (0 none, 1 the matrix segment, 2 the vector segment)
-#ifndef CTMI_W32_PRIO
-#define CTMI_W32_PRIO 1
-#endif
+constexpr int W32_BWD_NW = 4, W32_BWD_NST = 2;
 #define LOG2E_F 1.4426950408889634f
 #define LN2_F 0.6931471805599453f
 
@@ -77,17 +47,12 @@ namespace {
 // F16 (round 5): the same kernels on IEEE-half operands — v_mfma_f32_32x32x16_f16, half conversions of P / dS and of the outputs; everything
 // between the matrix instructions (scores, statistics, masks as C operands) is fp32 and does not change
 template <bool F16> __device__ __forceinline__ f32x16 mfma32(short8 a, short8 b, f32x16 c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_w32, a), __builtin_bit_cast(f16x8_w32, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_w32, a), __builtin_bit_cast(bf16x8_w32, b), c, 0, 0, 0);
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }
 template <bool F16> __device__ __forceinline__ uint32_t pk2(float lo, float hi) { if constexpr (F16) return pack_h2(lo, hi); else return pack_bf2(lo, hi); }
 template <bool F16> __device__ __forceinline__ float el2f(short x) {
     if constexpr (F16) { f16_t h; h.v = (uint16_t)x; return h2f(h); } else return bf2f((bf16_t)x);
-}
-__device__ __forceinline__ float max3(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
 }
 // value of the partner lane (l ^ 32) combined with the own one: v_permlane32_swap exchanges the upper 32 lanes of its first
 // operand with the lower 32 of its second, so with both operands = v every lane ends up holding {own, partner} in {a, b}
@@ -95,17 +60,12 @@ __device__ __forceinline__ float max3(float a, float b, float c) {
 __device__ __forceinline__ float pair_max(float v) {
     float a = v, b = v;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return max3(a, a, b);
+    return max3f(a, a, b);
 }
 __device__ __forceinline__ float pair_sum(float v) {
     float a = v, b = v;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
     return a + b;
-}
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_dst /* wave-uniform LDS byte address */) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 template <int N> __device__ __forceinline__ void wait_vm() {
     static_assert(N == 0 || N == 2 || N == 4 || N == 8, "counted waits are spelled out");
@@ -119,14 +79,6 @@ template <int N> __device__ __forceinline__ void wait_vm() {
 // issued a moment earlier) and serialises the whole pipeline on L2/HBM latency (measured: the loop ran at 1/4 of its speed).
 __device__ __forceinline__ void pin(short8& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ void pin(float& v) { asm volatile("" : "+v"(v)); }
-template <typename V> __device__ __forceinline__ V ldg1(const void* p) {
-    typedef const __attribute__((address_space(1))) V* gptr;
-    return *(gptr)(p);
-}
-__device__ __forceinline__ uint2 lds_tr16(const unsigned char* p) {
-    typedef __attribute__((address_space(3))) short4_w32 lds_v4;
-    return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(unsigned)(size_t)p));
-}
 template <bool F16> __device__ __forceinline__ short8 pack8(float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7) {
     return __builtin_bit_cast(short8, make_uint4(pk2<F16>(a0, a1), pk2<F16>(a2, a3), pk2<F16>(a4, a5), pk2<F16>(a6, a7)));
 }
@@ -165,8 +117,8 @@ struct WT {
         const int row = rbase + 4 * (gi >> 1) + (i >> 2);
         const int c = db * 4 + 2 * (gi & 1) + ((i >> 1) & 1);
         const int byte = (i & 1) * 8;
-        const uint2 lo = lds_tr16(tile + off(row, c) + byte);
-        const uint2 hi = lds_tr16(tile + off(row + 8, c) + byte);
+        const uint2 lo = lds_read_tr_b16(tile + off(row, c) + byte);
+        const uint2 hi = lds_read_tr_b16(tile + off(row + 8, c) + byte);
         return __builtin_bit_cast(short8, make_uint4(lo.x, lo.y, hi.x, hi.y));
     }
 };
@@ -257,7 +209,7 @@ __device__ __forceinline__ void mfma_results_fence() {
 template <int HD, int NW, bool REPLACE, bool F16 = false>       // REPLACE: future scores are REPLACED by a value other than finfo.min (GPT-2's -1e4); F16: IEEE-half operands
 __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) void attn32_fwd_kernel(AttnP p) {
     using W = WT<HD, NW>;
-    constexpr int NDS = HD / 16, NDB = HD / 32, TILE = W::TILE, STAGE = 2 * TILE, NPC = W::NPC, RPB = 32 * NW, NST = CTMI_W32_FWD_NST;
+    constexpr int NDS = HD / 16, NDB = HD / 32, TILE = W::TILE, STAGE = 2 * TILE, NPC = W::NPC, RPB = 32 * NW, NST = W32_FWD_NST;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* kbS = reinterpret_cast<float*>(smem + NST * STAGE);              // per-key bias / scale  (finfo.min: padding key)
     const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, hi = lane >> 5;
@@ -287,9 +239,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) voi
     auto issue = [&](int stage) {
         const unsigned d = lds0 + stage * STAGE + wid * NPC * 1024;
 #pragma unroll
-        for (int j = 0; j < NPC; ++j) { dma16(pk[j], d + j * 1024); pk[j] += kstep; }
+        for (int j = 0; j < NPC; ++j) { glds16(pk[j], d + j * 1024); pk[j] += kstep; }
 #pragma unroll
-        for (int j = 0; j < NPC; ++j) { dma16(pv[j], d + TILE + j * 1024); pv[j] += vstep; }
+        for (int j = 0; j < NPC; ++j) { glds16(pv[j], d + TILE + j * 1024); pv[j] += vstep; }
     };
     issue(0);
     if (NST >= 3 && ntiles > 1) issue(1);
@@ -304,7 +256,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) voi
 #pragma unroll
     for (int ds = 0; ds < NDS; ++ds) {
         qf[ds] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-        if (active) qf[ds] = ldg1<short8>(qp + (int64_t)(q0w + l32) * p.q_rs + ds * 16 + hi * 8);
+        if (active) qf[ds] = ldg_as1<short8>(qp + (int64_t)(q0w + l32) * p.q_rs + ds * 16 + hi * 8);
     }
     __syncthreads();
 #pragma unroll
@@ -318,20 +270,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) voi
     float m = -INFINITY, lsum = 0.f;                                         // m in raw units
     const float c = p.scale * LOG2E_F;
     const float ffr = p.future_fill <= FINFO_MIN ? FINFO_MIN : p.future_fill / p.scale;
-#if CTMI_W32_TIMING
-    uint32_t tX = 0, tY = 0, tBX = 0, tBY = 0, tPro = 0;
-    uint64_t tlast = __builtin_amdgcn_s_memtime();
-    const uint64_t tbeg = tlast;
-#endif
     int st = 0;
     for (int t = 0; t < ntiles; ++t) {
         // ring of NST stages, NST - 1 tiles in flight: tile t + NST - 1 goes out right after the barrier that retires tile t - 1
         if (NST >= 3 && t + 1 < ntiles) wait_vm<2 * NPC>(); else wait_vm<0>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        W32_TICK(tY);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        W32_TICK(tBX);
         if (t + NST - 1 < ntiles) issue(st == 0 ? NST - 1 : st - 1);
         if (t <= my_last) {
             const unsigned char* ks = smem + st * STAGE;
@@ -372,20 +317,15 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) voi
                 W32_FILL(0, 0); W32_FILL(0, 1); W32_FILL(0, 2); W32_FILL(0, 3); W32_FILL(1, 0); W32_FILL(1, 1); W32_FILL(1, 2); W32_FILL(1, 3);
 #undef W32_FILL
             }
-            float mx0 = max3(x[0][0], x[0][1], x[0][2]), mx1 = max3(x[0][8], x[0][9], x[0][10]);
-            float mx2 = max3(x[1][0], x[1][1], x[1][2]), mx3 = max3(x[1][8], x[1][9], x[1][10]);
-            mx0 = max3(mx0, x[0][3], x[0][4]); mx1 = max3(mx1, x[0][11], x[0][12]); mx2 = max3(mx2, x[1][3], x[1][4]); mx3 = max3(mx3, x[1][11], x[1][12]);
-            mx0 = max3(mx0, x[0][5], x[0][6]); mx1 = max3(mx1, x[0][13], x[0][14]); mx2 = max3(mx2, x[1][5], x[1][6]); mx3 = max3(mx3, x[1][13], x[1][14]);
-            mx0 = max3(mx0, x[0][7], x[0][15]); mx2 = max3(mx2, x[1][7], x[1][15]);
-            float mx = max3(mx0, mx1, mx2);
-            mx = max3(mx, mx, mx3);
+            float mx0 = max3f(x[0][0], x[0][1], x[0][2]), mx1 = max3f(x[0][8], x[0][9], x[0][10]);
+            float mx2 = max3f(x[1][0], x[1][1], x[1][2]), mx3 = max3f(x[1][8], x[1][9], x[1][10]);
+            mx0 = max3f(mx0, x[0][3], x[0][4]); mx1 = max3f(mx1, x[0][11], x[0][12]); mx2 = max3f(mx2, x[1][3], x[1][4]); mx3 = max3f(mx3, x[1][11], x[1][12]);
+            mx0 = max3f(mx0, x[0][5], x[0][6]); mx1 = max3f(mx1, x[0][13], x[0][14]); mx2 = max3f(mx2, x[1][5], x[1][6]); mx3 = max3f(mx3, x[1][13], x[1][14]);
+            mx0 = max3f(mx0, x[0][7], x[0][15]); mx2 = max3f(mx2, x[1][7], x[1][15]);
+            float mx = max3f(mx0, mx1, mx2);
+            mx = max3f(mx, mx, mx3);
             mx = pair_max(mx);
-            float m_new = max3(m, m, mx);                                    // finite: every tile holds >= 1 existing key
-            if (CTMI_W32_DEFER_MAX > 0) {
-                // keep the old reference while no row maximum of the wave grew by more than 2^DEFER: the probabilities of this tile are
-                // then bounded by 2^DEFER instead of 1 (bf16 is a floating format: no precision is lost), O and l stay in the old scale
-                if (!__any((mx - m) * c > (float)CTMI_W32_DEFER_MAX)) m_new = m;
-            }
+            float m_new = max3f(m, m, mx);                                    // finite: every tile holds >= 1 existing key
             const float alpha = __builtin_amdgcn_exp2f((m - m_new) * c);
             const float mc = m_new * c;
             if (allk) {
@@ -433,7 +373,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) voi
 #pragma unroll
                     for (int db = 0; db < NDB; ++db) o[db] = mfma32<F16>(W::fragT(vs, kk * 32 + 16 * s, db, lane), pb[kk][s], o[db]);
         }
-        W32_TICK(tX);
         st = st == NST - 1 ? 0 : st + 1;
     }
     lsum = pair_sum(lsum);
@@ -446,11 +385,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) voi
             const int64_t srow = (b * p.nh + h) * p.Sq + q0w + l32;
             p.stat_m[srow] = m <= FINFO_MIN ? FINFO_MIN : m * p.scale;
             p.stat_l[srow] = lsum;
-#if CTMI_W32_TIMING
-            const uint32_t tot = (uint32_t)(__builtin_amdgcn_s_memtime() - tbeg);
-            const uint32_t v[8] = {tX, tY, tBX, tBY, tPro, tot, (uint32_t)ntiles, (uint32_t)(my_last + 1)};
-            if (l32 < 8) p.stat_l[srow] = (float)v[l32];
-#endif
         }
     }
 }
@@ -461,7 +395,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) voi
 template <int HD, int NW, bool F16 = false>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) void attn32_dq_kernel(AttnP p) {
     using W = WT<HD, NW>;
-    constexpr int NDS = HD / 16, NDB = HD / 32, TILE = W::TILE, STAGE = 2 * TILE, NPC = W::NPC, RPB = 32 * NW, NST = CTMI_W32_BWD_NST;
+    constexpr int NDS = HD / 16, NDB = HD / 32, TILE = W::TILE, STAGE = 2 * TILE, NPC = W::NPC, RPB = 32 * NW, NST = W32_BWD_NST;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* kbS = reinterpret_cast<float*>(smem + NST * STAGE);
     const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, hi = lane >> 5;
@@ -491,9 +425,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) voi
     auto issue = [&](int stage) {
         const unsigned d = lds0 + stage * STAGE + wid * NPC * 1024;
 #pragma unroll
-        for (int j = 0; j < NPC; ++j) { dma16(pk[j], d + j * 1024); pk[j] += kstep; }
+        for (int j = 0; j < NPC; ++j) { glds16(pk[j], d + j * 1024); pk[j] += kstep; }
 #pragma unroll
-        for (int j = 0; j < NPC; ++j) { dma16(pv[j], d + TILE + j * 1024); pv[j] += vstep; }
+        for (int j = 0; j < NPC; ++j) { glds16(pv[j], d + TILE + j * 1024); pv[j] += vstep; }
     };
     issue(0);
     if (NST >= 3 && ntiles > 1) issue(1);
@@ -514,9 +448,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (HD == 64 ? 3 : 2) : NW / 4) voi
         const int64_t ro = (int64_t)(q0w + l32) * p.o_rs;
 #pragma unroll
         for (int ds = 0; ds < NDS; ++ds) {
-            qf[ds] = ldg1<short8>(qp + (int64_t)(q0w + l32) * p.q_rs + ds * 16 + hi * 8);
-            gf[ds] = ldg1<short8>(gp + ro + ds * 16 + hi * 8);
-            const short8 of = ldg1<short8>(op + ro + ds * 16 + hi * 8);
+            qf[ds] = ldg_as1<short8>(qp + (int64_t)(q0w + l32) * p.q_rs + ds * 16 + hi * 8);
+            gf[ds] = ldg_as1<short8>(gp + ro + ds * 16 + hi * 8);
+            const short8 of = ldg_as1<short8>(op + ro + ds * 16 + hi * 8);
 #pragma unroll
             for (int j = 0; j < 8; ++j) dl += el2f<F16>(gf[ds][j]) * el2f<F16>(of[j]);
         }
@@ -633,7 +567,7 @@ template <int HD, int NW, bool F16 = false, int MODE = 0>
 __global__ __launch_bounds__(NW * 64, (NW == 4 && (HD == 64 || MODE != 0)) ? 2 : NW / 4) void attn32_dkdv_kernel(AttnP p) {
     constexpr bool DO_DV = MODE != 2, DO_DK = MODE != 1;
     using W = WT<HD, NW>;
-    constexpr int NDS = HD / 16, NDB = HD / 32, TILE = W::TILE, STAGE = 2 * TILE, NPC = W::NPC, RPB = 32 * NW, NST = CTMI_W32_BWD_NST;
+    constexpr int NDS = HD / 16, NDB = HD / 32, TILE = W::TILE, STAGE = 2 * TILE, NPC = W::NPC, RPB = 32 * NW, NST = W32_BWD_NST;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // per-query statistics, see lds_qg(): [Sq] score offset | [Sq] delta (not in the dV pass, which has no dS)
     float* m2S = reinterpret_cast<float*>(smem + NST * STAGE);
@@ -668,9 +602,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && (HD == 64 || MODE != 0)) ? 2 :
     auto issue = [&](int stage) {
         const unsigned d = lds0 + stage * STAGE + wid * NPC * 1024;
 #pragma unroll
-        for (int j = 0; j < NPC; ++j) { dma16(pq[j], d + j * 1024); pq[j] += qstep; }
+        for (int j = 0; j < NPC; ++j) { glds16(pq[j], d + j * 1024); pq[j] += qstep; }
 #pragma unroll
-        for (int j = 0; j < NPC; ++j) { dma16(pg[j], d + TILE + j * 1024); pg[j] += gstep; }
+        for (int j = 0; j < NPC; ++j) { glds16(pg[j], d + TILE + j * 1024); pg[j] += gstep; }
     };
     if (nt > 0) issue(0);
     if (NST >= 3 && nt > 1) issue(1);
@@ -703,8 +637,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && (HD == 64 || MODE != 0)) ? 2 :
         const int64_t key = k0w + l32;
 #pragma unroll
         for (int ds = 0; ds < NDS; ++ds) {
-            kf[ds] = ldg1<short8>(kp + key * p.k_rs + ds * 16 + hi * 8);
-            if constexpr (DO_DK) vf[ds] = ldg1<short8>(vp + key * p.v_rs + ds * 16 + hi * 8);
+            kf[ds] = ldg_as1<short8>(kp + key * p.k_rs + ds * 16 + hi * 8);
+            if constexpr (DO_DK) vf[ds] = ldg_as1<short8>(vp + key * p.v_rs + ds * 16 + hi * 8);
             else vf[ds] = short8{0, 0, 0, 0, 0, 0, 0, 0};
         }
         const float slope2 = p.slopes ? p.slopes[h] * LOG2E_F : 0.f;
@@ -883,12 +817,12 @@ extern "C" int ctmi_attn_set_path(int mask) {
 int ctmi_attn32_fwd(const AttnP& p, hipStream_t st, int f16) {
     if (!w32_ok(p) || !(w32_mask() & 1)) return 0;
     const int64_t BH = p.B * p.nh;
-    constexpr int NW = CTMI_W32_FWD_NW, RPB = 32 * NW;
+    constexpr int NW = W32_FWD_NW, RPB = 32 * NW;
     const bool replace = p.future_fill > FINFO_MIN;
     const int64_t grid = ((p.Sq + RPB - 1) / RPB) * BH;
     ctmi_by_flags([&](auto f16c, auto hd64, auto rep) {
         constexpr int HD = decltype(hd64)::value ? 64 : 128;
-        launch32(&attn32_fwd_kernel<HD, NW, decltype(rep)::value, decltype(f16c)::value>, grid, 64 * NW, lds_kv<HD, NW>(p, CTMI_W32_FWD_NST), st, p);
+        launch32(&attn32_fwd_kernel<HD, NW, decltype(rep)::value, decltype(f16c)::value>, grid, 64 * NW, lds_kv<HD, NW>(p, W32_FWD_NST), st, p);
     }, f16 != 0, p.hd == 64, replace);
     return 1;
 }
@@ -902,7 +836,7 @@ int ctmi_attn32_bwd(const AttnP& p, hipStream_t st, int f16) {
     if (!w32_ok(p) || !(w32_mask() & 2)) return 0;
     const int64_t BH = p.B * p.nh;
     // dQ first: it also publishes delta = rowsum(dO * O) for the dK/dV kernel (same stream: ordered)
-    constexpr int NW = CTMI_W32_BWD_NW, RPB = 32 * NW, NST = CTMI_W32_BWD_NST;
+    constexpr int NW = W32_BWD_NW, RPB = 32 * NW, NST = W32_BWD_NST;
     const int64_t gq = ((p.Sq + RPB - 1) / RPB) * BH, gk = ((p.Sk + RPB - 1) / RPB) * BH;
     ctmi_by_flags([&](auto f16c, auto hd64) {
         constexpr bool F16 = decltype(f16c)::value;

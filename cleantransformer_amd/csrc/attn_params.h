@@ -17,7 +17,7 @@ struct AttnP {
     float drop_scale;        // 1 / (1 - p)
     float future_fill;       // score of a (query, key) pair in the causal future whose key may be attended: FINFO_MIN (Bloom masked_fill) or GPT's -1e4
     int causal, off, vec_ok;
-    int dbg;                 // timing experiments only (CTMI_ATTN_DBG): 1 = no steady-state global loads, 2 = no LDS restage
+    int reserved_;           // always 0: keeps the kernel-argument block at its size (344 bytes), which is part of every attention kernel's metadata
 };
 
 // fast path (attention_w32.hip): returns 1 when it launched the kernels, 0 when the problem is outside its envelope (the

@@ -14,8 +14,13 @@ typedef uint16_t bf16_t;                                   // raw bfloat16 bits
 // weight gradients and the 128-row attention kernels have fp16 twins of their bf16 forms (same schedules, the f16 MFMA), like every other kernel.
 struct f16_t { uint16_t v; };
 typedef short  short8 __attribute__((ext_vector_type(8)));   // 8 x bf16 MFMA operand (4 VGPRs)
-typedef short  short4v __attribute__((ext_vector_type(4)));
+typedef short  short4_t __attribute__((ext_vector_type(4)));
 typedef float  f32x4 __attribute__((ext_vector_type(4)));    // 16x16 MFMA accumulator
+typedef float  f32x2 __attribute__((ext_vector_type(2)));    // operand pair of the packed fp32 instructions (v_pk_mul/fma/add_f32) and conversions
+// 16 bytes of data in flight: a first-class vector, NOT the uint4 struct — struct copies become memcpy intrinsics that SROA left in private
+// memory (scratch stores + vmcnt(0) after every attention tile load) once the scalar gather path was compiled out
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 #define WAVE 64
 #define FINFO_MIN (-3.4028234663852886e+38f)                // torch.finfo(torch.float32).min
@@ -35,10 +40,9 @@ bool ctmi_take_attr_error();                               // true once after a 
 __device__ __forceinline__ float bf2f(bf16_t x) { return __uint_as_float(((uint32_t)x) << 16); }
 // fp32 -> bf16, round-to-nearest-even: the native conversion, which hipcc lowers to gfx950's v_cvt_pk_bf16_f32
 typedef __bf16 bf16x2_native __attribute__((ext_vector_type(2)));
-typedef float f32x2_native __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ bf16_t f2bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
 __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
-    const f32x2_native v = {lo, hi};
+    const f32x2 v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_native));
 }
 
@@ -46,7 +50,7 @@ __device__ __forceinline__ float h2f(f16_t x) { return (float)__builtin_bit_cast
 __device__ __forceinline__ f16_t f2h(float f) { f16_t r; r.v = __builtin_bit_cast(uint16_t, (_Float16)f); return r; }     // round-to-nearest-even, overflow -> inf (what a loss scaler looks for)
 typedef _Float16 f16x2_native __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack_h2(float lo, float hi) {
-    const f32x2_native v = {lo, hi};
+    const f32x2 v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_native));
 }
 __device__ __forceinline__ void unpack_h2(uint32_t w, float& lo, float& hi) {
@@ -100,44 +104,22 @@ template <> __device__ __forceinline__ uint32_t pack2<f16_t>(float lo, float hi)
 // computes, the line is dropped from the XCD's L2 — the consumers of a [T, *] activation run on all eight XCDs and read it from the Infinity Cache
 // either way).  Kernels whose outputs are streamed once and read by the NEXT kernels (GEMM epilogues, LayerNorm, attention) store through these.
 // The asm ends in `s_nop 1`: hipcc's hazard recognizer does not see into asm, and a 16-byte store needs a wait state before its data registers may
-// be overwritten (cdna_hip_programming.md 5.7 item 1).  -DCTMI_ST_WT=0 restores plain stores (A/B builds).
-#ifndef CTMI_ST_WT
-#define CTMI_ST_WT 1
-#endif
-typedef uint32_t ctmi_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t ctmi_u32x2 __attribute__((ext_vector_type(2)));
+// be overwritten (cdna_hip_programming.md 5.7 item 1).
 __device__ __forceinline__ void st_wt16(void* p, const uint4& v) {
-#if CTMI_ST_WT
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(ctmi_u32x4{v.x, v.y, v.z, v.w}) : "memory");
-#else
-    *reinterpret_cast<uint4*>(p) = v;
-#endif
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(u32x4{v.x, v.y, v.z, v.w}) : "memory");
 }
-// fp32 outputs (weight gradients: 32-byte row pieces per lane, two store instructions per 128-byte line) stay write-back: written through, every
-// half-filled line went out twice — the grouped weight-gradient launch 213 -> 232 us (profiles/r06_boundary_dirty.txt)
-#ifndef CTMI_ST_WT_F32
-#define CTMI_ST_WT_F32 0
-#endif
-__device__ __forceinline__ void st_wt16(void* p, const f32x4& v) {
-#if CTMI_ST_WT && CTMI_ST_WT_F32
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
-#else
-    *reinterpret_cast<f32x4*>(p) = v;
-#endif
-}
+// fp32 outputs (weight gradients: 32-byte row pieces per lane, two store instructions per 128-byte line) stay write-back, so this overload is
+// a plain store: written through, every half-filled line went out twice — the grouped weight-gradient launch 213 -> 232 us
+// (profiles/r06_boundary_dirty.txt)
+__device__ __forceinline__ void st_wt16(void* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
 __device__ __forceinline__ void st_wt8(void* p, const uint2& v) {
-#if CTMI_ST_WT
-    asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 0" :: "v"(p), "v"(ctmi_u32x2{v.x, v.y}) : "memory");
-#else
-    *reinterpret_cast<uint2*>(p) = v;
-#endif
+    asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 0" :: "v"(p), "v"(u32x2{v.x, v.y}) : "memory");
 }
 
 // ---------------------------------------------------------------- streaming (non-temporal) 16-byte accesses
 // For single-pass kernels whose data is far larger than the 256 MiB Infinity Cache (the optimizer walks 16.8 GB per step, the loss backward
 // 8.2 GB): no line is ever reused, so none should be kept.
 typedef float f32x4_nt __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_nt __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ldg_stream(const float* p) {
     const f32x4_nt v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt*>(p));
     return make_float4(v[0], v[1], v[2], v[3]);
@@ -147,14 +129,38 @@ __device__ __forceinline__ void stg_stream(float* p, const float4& v) {
 }
 
 __device__ __forceinline__ uint4 ldg_stream16(const void* p) {
-    const u32x4_nt v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_nt*>(p));
+    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
     return make_uint4(v[0], v[1], v[2], v[3]);
 }
 __device__ __forceinline__ void stg_stream16(void* p, const uint4& v) {
-    __builtin_nontemporal_store(u32x4_nt{v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4_nt*>(p));
+    __builtin_nontemporal_store(u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4*>(p));
+}
+
+// ---------------------------------------------------------------- loads and LDS-DMA with the address space spelled out
+// Loads through pointers that hipcc cannot prove to be global (loop-carried / selected pointers derived from the by-value
+// kernel-argument struct) are emitted as flat_load, and a FLAT access counts on LGKM_CNT as well as VM_CNT: every
+// `s_waitcnt lgkmcnt(0)` in front of an MFMA (placed there for the LDS fragment reads) then also waited for the tile prefetch
+// issued just before it — the software pipeline was serialised on HBM/L2 latency in all three general attention kernels.  This helper
+// casts to the global address space explicitly, so the loads are global_load_* and only the vmcnt wait at their use sees them.
+template <typename V> __device__ __forceinline__ V ldg_as1(const void* p) {
+    typedef const __attribute__((address_space(1))) V* gptr;
+    return *(gptr)(p);
+}
+// One piece of LDS-DMA: 64 lanes x 16 bytes from per-lane global addresses to 1 KiB of LDS at a wave-uniform base (M0) + lane * 16.  Inline asm,
+// so hipcc neither counts nor drains it: the callers wait with counted s_waitcnt vmcnt(N).
+__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst /* wave-uniform LDS byte address */) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
 // ---------------------------------------------------------------- wave / block reductions
+// 3-input max in ONE instruction.  (fmaxf on MFMA results makes hipcc insert a canonicalising v_max x,x per operand.)
+__device__ __forceinline__ float max3f(float a, float b, float c) {
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -173,7 +179,6 @@ __device__ __forceinline__ float wave_max(float v) {
 // with s = 1 / (1 + 2^z), z = -x (c1 + c2 x^2), c1 = 2*0.79788456*log2(e), c2 = 0.044715 c1: one v_exp_f32 and one
 // v_rcp_f32 per element (abs error ~1e-7) and about half the VALU work of the tanh form; the f32x2 versions compile to
 // v_pk_mul/fma/add_f32.  The GEMM epilogues that apply them are not hidden behind MFMA work, so their length matters.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 gelu_sigma_pk(f32x2 x, f32x2 x2) {
     const f32x2 z = -x * (x2 * 0.10294324f + 2.3022082f);
     const f32x2 d = f32x2{__builtin_amdgcn_exp2f(z[0]), __builtin_amdgcn_exp2f(z[1])} + 1.0f;

@@ -23,12 +23,6 @@
 #ifndef CTMI_GEMM_PART
 #define CTMI_GEMM_PART (-1)
 #endif
-#ifndef CTMI_GELU_AUX_WT
-#define CTMI_GELU_AUX_WT 0      // 1: the GELU pre-activation written through (sc1) instead of non-temporally — measured slower in the step, kept for A/B builds
-#endif
-#ifndef CTMI_SIDE_PRE8
-#define CTMI_SIDE_PRE8 1      // round 6: the 256-row ping-pong tile prefetches its epilogue's side input too (0: rounds 3-5 — such epilogues forced onto the 128-row tile)
-#endif
 #define CTMI_GEMM_HAS(p) (CTMI_GEMM_PART == -1 || CTMI_GEMM_PART == (p))
 
 // LDS-DMA ring depth and epilogue re-layout of the bf16 fast path (gemm_glds_kernel below).
@@ -50,14 +44,6 @@ template <typename T> struct Tile;
 template <> struct Tile<bf16_t> { static constexpr int BM = 128, BN = 128, BK = 64, PADK = 8, PADR = 8; };
 template <> struct Tile<f16_t>  { static constexpr int BM = 128, BN = 128, BK = 64, PADK = 8, PADR = 8; };     // (fp16: the register-staged kernel only)
 template <> struct Tile<float>  { static constexpr int BM = 128, BN = 128, BK = 16, PADK = 4, PADR = 4; };
-
-typedef short short4_t __attribute__((ext_vector_type(4)));
-// ds_read_b64_tr_b16 through the compiler builtin (hipcc then tracks its lgkmcnt itself)
-__device__ __forceinline__ uint2 lds_read_tr_b16(const void* p) {
-    typedef __attribute__((address_space(3))) short4_t lds_v4;
-    const short4_t r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(unsigned)(size_t)p);
-    return __builtin_bit_cast(uint2, r);
-}
 
 // LDS image of one operand tile.  !KMAJOR: [ROWS][BK+PADK] (k contiguous).  KMAJOR: [BK][ROWS+PADR] (rows contiguous).
 template <typename T, bool KMAJOR, int ROWS>
@@ -202,7 +188,6 @@ template <int WM> struct GrpRegs<true, WM, true> { f32x4 accs; bool cs_on; f32x4
 #define WG_ONES8 (std::is_same<T, f16_t>::value ? short8{0x3C00, 0x3C00, 0x3C00, 0x3C00, 0x3C00, 0x3C00, 0x3C00, 0x3C00} \
                                                 : short8{0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80})   /* eight 1.0 in the operand type (half: 0x3C00, bf16: 0x3F80) */
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 template <typename TO> __device__ __forceinline__ void store4(TO* p, const float* v);
 template <> __device__ __forceinline__ void store4<float>(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
 template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, const float* v) { *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])); }
@@ -401,11 +386,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
 //     s_barrier per K-step orders LDS-DMA writes against the other waves' reads.  The DMA instructions are inline
 //     asm, so hipcc neither counts nor drains them.
 // Requires: bf16, 16-byte aligned operands, K % 32 == 0 (per split).  Anything else takes the v1 kernel above.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst /* wave-uniform LDS byte address */) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 __device__ __forceinline__ int swz4(int key) { return (0x78 >> (2 * key)) & 3; }          // {0,2,3,1}: see GTile<false>
 __device__ __forceinline__ int kkey(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
 
@@ -622,7 +602,7 @@ __device__ __forceinline__ void glds_body(const GA g) {   // (by value: through 
                              "v_permlane16_swap_b32 %3, %7"
                              : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3));
                 float* d = Cl + (int64_t)arow(i) * ldc + 32 * jp;
-                st_wt16(d, f32x4{a0, a1, a2, a3});
+                st_wt16(d, f32x4{a0, a1, a2, a3});                               // fp32 slab / weight-gradient rows: the write-back overload (common.h)
                 st_wt16(d + 4, f32x4{b0, b1, b2, b3});
             }
         if (gs.cs_on) {
@@ -693,7 +673,7 @@ __device__ __forceinline__ void glds_body(const GA g) {   // (by value: through 
             // RES) is fetched one pass ahead, into the registers the previous pass's accumulators just freed: loaded
             // where it is used, each of the 16 row groups of a tile would expose a full global-load latency
             // (only the 128-row tiles have the registers for it: with 128 accumulators live hipcc spills the prefetch)
-            constexpr bool PRE_AUX = (EPI == CTMI_EPI_DGELU || EPI == CTMI_EPI_DRELU || EPI == CTMI_EPI_MUL) && (WM == 4 || CTMI_SIDE_PRE8);
+            constexpr bool PRE_AUX = (EPI == CTMI_EPI_DGELU || EPI == CTMI_EPI_DRELU || EPI == CTMI_EPI_MUL) ;   // (round 6: the 256-row ping-pong tile prefetches it too, see pick_tile)
             constexpr bool PRE_RES = RES && !PRE_AUX && WM == 4;
             constexpr bool PRE = PRE_AUX || PRE_RES;
             const T* side = PRE_AUX ? AUXI : R;
@@ -711,8 +691,8 @@ __device__ __forceinline__ void glds_body(const GA g) {   // (by value: through 
                     // the pre-activation is kept for the BACKWARD only (a whole forward and half a backward away): CTMI_GELU_AUX_NT writes it
                     // non-temporally, so that the activation next to it — the A operand of the very next GEMM — is what stays in the caches
                     // (same box, interleaved: forward chain of 24 blocks 6.16 / 6.26 -> 6.07 / 6.05 ms, step 37.01-37.35 -> 36.83-37.08 ms)
-                    if constexpr (sizeof(T) == 2 && CTMI_GELU_AUX_WT) st_wt16(AUXO + off, tb);                 // (-DCTMI_GELU_AUX_WT=1, A/B builds only: written through like the tile itself — measured +0.2 ms per step against the non-temporal store below, profiles/r06_boundary_dirty.txt)
-                    else if constexpr (sizeof(T) == 2) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, tb), reinterpret_cast<u32x4*>(AUXO + off));   // (the builtin, not asm: hipcc's hazard recognizer does not see into asm, and a first asm version — no wait state between the 16-byte store and the next write of its data registers — stored garbage in a few rows; tests/test_gpu_ops.py::test_gemm_at_the_step_shapes_sampled_vs_fp64 caught it)
+                    // (written through like the tile itself it measured +0.2 ms per step against the non-temporal store, profiles/r06_boundary_dirty.txt)
+                    if constexpr (sizeof(T) == 2) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, tb), reinterpret_cast<u32x4*>(AUXO + off));   // (the builtin, not asm: hipcc's hazard recognizer does not see into asm, and a first asm version — no wait state between the 16-byte store and the next write of its data registers — stored garbage in a few rows; tests/test_gpu_ops.py::test_gemm_at_the_step_shapes_sampled_vs_fp64 caught it)
                     else *reinterpret_cast<uint4*>(AUXO + off) = tb;
                     unpack16<T>(tb, v);
 #pragma unroll
@@ -773,7 +753,7 @@ __device__ __forceinline__ void glds_body(const GA g) {   // (by value: through 
                             for (int r = 0; r < 4; ++r) { v[r] += c0v[r]; v[4 + r] += c1v[r]; }
                         }
                     }
-                    st_wt16(Cf, f32x4{v[0], v[1], v[2], v[3]});
+                    st_wt16(Cf, f32x4{v[0], v[1], v[2], v[3]});                  // fp32 output rows: the write-back overload (common.h)
                     st_wt16(Cf + 4, f32x4{v[4], v[5], v[6], v[7]});
                 } else {
                     if constexpr (!PLAIN) {
@@ -1360,9 +1340,9 @@ static void glds_launch(GemmArgs& g, hipStream_t st) {
     // Long tiles are launched one workgroup per tile even under the persistent policy: the prefetch across tile boundaries is worth ~2 us per
     // tile, nothing against a 256-K-step tile, and workgroups that the dispatcher starts in order stay closer together than persistent ones
     // that drift over 15 tiles each — the four column tiles that share a dlogits panel of the LM-head weight gradient then find it in their
-    // XCD's L2: FETCH 13.2 -> 8.6 GB per launch, 3.47 -> 3.45 ms (profiles/r05_lmhead_wgrad_launch.txt).  CTMI_GEMM_PERSIST_KSTEPS overrides (0: no limit).
-    static const int persist_ksteps = ctmi_env_int("CTMI_GEMM_PERSIST_KSTEPS", 128);
-    const bool long_tiles = persist_ksteps > 0 && g.k_per_split / 32 > persist_ksteps;
+    // XCD's L2: FETCH 13.2 -> 8.6 GB per launch, 3.47 -> 3.45 ms (profiles/r05_lmhead_wgrad_launch.txt).
+    constexpr int PERSIST_KSTEPS = 128;
+    const bool long_tiles = g.k_per_split / 32 > PERSIST_KSTEPS;
     const unsigned grid = (unsigned)((persist && !long_tiles && nwork > slots) ? slots : nwork);
     if constexpr (std::is_same<TE, f16_t>::value) {
         auto kern = &gemm_glds_kernel_f16<TO, AK, BKM, EPI, WM, WGN, PP, RES, XLANE>;
@@ -1431,23 +1411,17 @@ extern "C" int ctmi_get_launch_policy(int* shared, int* reserve_cus) {
 
 constexpr int64_t WGRAD_ITEMS = 256;     // round-3 rule (CTMI_WGRAD_RULE=0): split-K target of the layer weight gradients, work items (tiles x splits) to aim for
 // layer weight-gradient rule (CTMI_WGRAD_RULE): 0 = round 3 (128x128 / 256x128 free-running tiles, co-resident with the data gradients),
-// 1 = 128x256 ping-pong unsplit, 2 (default since round 4) = the same with split-K up to CTMI_WGRAD_ITEMS4 (128) work items: at Bloom-560M the
+// 1 = 128x256 ping-pong unsplit, 2 (default since round 4) = the same with split-K up to WGRAD_ITEMS4 (128) work items: at Bloom-560M the
 // QKV gradient (96 tiles) splits two ways, the dense one (32 tiles) four ways, the two [4H,H] ones (128 tiles) stay whole
 static int wgrad_rule() {
     static const int v = std::max(0, ctmi_env_int("CTMI_WGRAD_RULE", 2));
     return v;
 }
-static int64_t wgrad_items4() {
-    static const int v = std::max(1, ctmi_env_int("CTMI_WGRAD_ITEMS4", 128));
-    return v;
-}
+constexpr int64_t WGRAD_ITEMS4 = 128;
 // smallest number of 256x256 output tiles for which a forward / data-gradient GEMM takes the 256-row ping-pong tile (below: 128x256 if
 // that fills the chip).  350 since round 1 (384 = the QKV forward: 1.5 rounds of 256 CUs on tile 3, 3 full rounds of 768 on tile 4);
-// CTMI_TILE3_MIN overrides it for sweeps — every rule of rounds 1-3 was measured with the K-loop drain of the cross-lane kernels in place.
-static int64_t tile3_min() {
-    static const int v = std::max(1, ctmi_env_int("CTMI_TILE3_MIN", 350));
-    return v;
-}
+// every rule of rounds 1-3 was measured with the K-loop drain of the cross-lane kernels in place.
+constexpr int64_t TILE3_MIN = 350;
 static void pick_tile(int64_t M, int64_t N, int64_t K, bool wgrad, bool bkm, int epi, int max_splits, int& tile, int& splits) {
     static const int force = ctmi_env_int("CTMI_GEMM_TILE", -1), force_split = ctmi_env_int("CTMI_GEMM_SPLIT", -1);
     if (force_split >= 1) max_splits = std::min(max_splits, force_split);
@@ -1470,21 +1444,19 @@ static void pick_tile(int64_t M, int64_t N, int64_t K, bool wgrad, bool bkm, int
         return;
     }
     if (wgrad) {
-        static const int nosplit = ctmi_env_int("CTMI_WGRAD_NOSPLIT", 0);
         // LM head: [V,H] — and its row windows: the data-parallel path produces the tied gradient in <= 64 MiB pieces of 15 360 / 16 384
         // rows (trainer/ddp.py chunk_rows: whole rounds of the CUs the policy leaves), 240 / 256 tiles of 256x256; the layer weight
         // gradients of this geometry have <= 64 such tiles (round-3 advisor: a piece used to fall to the unsplit 128x128 rule below)
         if (t1 >= 1024 || (t2 >= 128 && M >= 8 * N)) tile = 3;                // (tall: a [rows, H] window, not a square layer gradient)
-        else if (nosplit) tile = nosplit == 2 ? 4 : 3;
         else if (wgrad_rule() >= 1) {
             // round 4: with the K-loop drain of the 128-row ping-pong kernels fixed AND the side stream no longer joined after every block
             // (ctmi_bloom_block_grads.defer_join) the layer weight gradients run fastest in the step on the 128x256 ping-pong tile, unsplit:
             // 96 / 32 / 128 / 128 workgroups that take whole CUs next to the data-gradient chain instead of sharing them — 37.33-37.49 vs
             // 38.10-38.17 ms with the round-3 rule below (128x128 free-running, co-resident), same box, interleaved (profiles/r04_wgrad_rule.txt).
-            // wgrad_rule() = 2 adds a split along K where that leaves fewer than CTMI_WGRAD_ITEMS4 work items: 37.30-37.38 vs 37.53-37.63 (128 items;
+            // wgrad_rule() = 2 adds a split along K where that leaves fewer than WGRAD_ITEMS4 work items: 37.30-37.38 vs 37.53-37.63 (128 items;
             // 256: 38.15-38.30, 64: 37.60-37.70).
             tile = 4;
-            if (wgrad_rule() >= 2) { while (splits < max_splits && t4 * splits < wgrad_items4() && K / (splits * 2) >= 1024) splits *= 2; }
+            if (wgrad_rule() >= 2) { while (splits < max_splits && t4 * splits < WGRAD_ITEMS4 && K / (splits * 2) >= 1024) splits *= 2; }
         }
         else {
             // round 3 (profiles/r03_gemm_tile_sweep.txt): a weight gradient with >= 256 tiles of 128x128 (h->4h and 4h->h) runs them
@@ -1500,7 +1472,7 @@ static void pick_tile(int64_t M, int64_t N, int64_t K, bool wgrad, bool bkm, int
             while (splits < max_splits && tiles * splits < items && K / (splits * 2) >= 1024) splits *= 2;
         }
     } else if (K >= 32768 && max_splits >= 2 && t2 * 2 >= 192) { tile = 3; splits = 2; }
-    else if (t2 >= tile3_min() || (t2 == 256 && K >= 2048)) tile = 3;             // (round 6: exactly ONE full round of 256x256 tiles with a long K — the [T,H] outputs of the Bloom-7B1 geometry, T = H = 4096:
+    else if (t2 >= TILE3_MIN || (t2 == 256 && K >= 2048)) tile = 3;             // (round 6: exactly ONE full round of 256x256 tiles with a long K — the [T,H] outputs of the Bloom-7B1 geometry, T = H = 4096:
                                                                                   // 204.2 -> 197.3 ms per step against two rounds of the 128-row tile, profiles/r06_bloom7b1_1gpu_bench.txt)
                                                                                   // (also where 256x256 tiles fill their last round badly — QKV forward: 384
                                                                                   // tiles = 1.5 rounds; onto 768 tiles of 128x256 it is +4 % alone and 0.1 ms WORSE in the step, round 4)
@@ -1510,7 +1482,6 @@ static void pick_tile(int64_t M, int64_t N, int64_t K, bool wgrad, bool bkm, int
     // epilogues that read a second [M,N] operand (activation-derivative input): rounds 3-5 only the 128-row ping-pong tile had the registers to
     // prefetch it a pass ahead (112 vs 121 us on the [T,4H] DGELU dgrad) and took these launches; round 6 the 256-row tile prefetches it through ONE
     // register slot (244 VGPRs, no scratch) and keeps them: 77 - 81 vs 88 - 90 us (profiles/r06_dgelu_side_input.txt)
-    if (!CTMI_SIDE_PRE8 && (epi == CTMI_EPI_DGELU || epi == CTMI_EPI_DRELU || epi == CTMI_EPI_MUL) && tile == 3) tile = 4;
     if (force >= 0) tile = force;
 }
 
@@ -1902,8 +1873,7 @@ extern "C" int ctmi_gemm(const void* A, int64_t lda, int a_kmajor, const void* B
     auto al = [](const void* p, int bytes) { return p == nullptr || ((((uintptr_t)p) & (bytes - 1)) == 0); };
     const int cbytes = (out_f32 || dtype == CTMI_F32) ? 16 : 8;
     g.vec_c = (ldc % 4 == 0) && al(C, cbytes) && al(residual, 4 * es) && al(aux_in, 4 * es) && al(aux_out, 4 * es) && al(bias, 16);
-    static const int nt_on = ctmi_env_int("CTMI_GEMM_NT", 1);
-    g.nt_c = nt_on && (M * N * (int64_t)((out_f32 || dtype == CTMI_F32) ? 4 : 2) > (1LL << 30)) ? 1 : 0;
+    g.nt_c = (M * N * (int64_t)((out_f32 || dtype == CTMI_F32) ? 4 : 2) > (1LL << 30)) ? 1 : 0;
     g.vec8 = g.vec_c && (ldc % 8 == 0) && al(C, 16) && al(residual, 16) && al(aux_in, 16) && al(aux_out, 16);   // 8-element rows (LDS-shuffled epilogue)
     // split-K: only for plain accumulations (weight gradients) that would leave most of the 256 CUs idle
     g.splits = 1; g.k_per_split = K; g.slabs = nullptr;

@@ -4,11 +4,6 @@
 #include "reduce_jobs.h"
 #include "prof.h"
 
-// CTMI_LN_BWD_PREFETCH: ln_bwd_vec keeps the loads of its next row in flight while it reduces and stores the current one (round 4).
-#ifndef CTMI_LN_BWD_PREFETCH
-#define CTMI_LN_BWD_PREFETCH 1
-#endif
-
 // ------------------------------------------------------------------------------------------------
 // LayerNorm  (transformer.py:71-89)
 // ------------------------------------------------------------------------------------------------
@@ -222,8 +217,9 @@ __global__ __launch_bounds__(64 * lnb_waves(MAXV)) void ln_bwd_vec(const T* __re
             }
         }
     };
+    // the loads of the next row stay in flight while the current one is reduced and stored (round 4)
     // (NS = 4 keeps one row at a time: with 32 more accumulators the two-set form needs all 256 registers and spills)
-    if (CTMI_LN_BWD_PREFETCH && NS == 2) {
+    if (NS == 2) {
         // two rows per trip over two register sets (A, B) — no copies between them: a copy of the prefetched row into "current" registers is
         // where hipcc placed its wait, i.e. at the bottom of the trip that had just issued the loads
         uint4 xa[MAXV], ga[MAXV], ra[MAXV], xb[MAXV], gb[MAXV], rb[MAXV];
@@ -445,10 +441,8 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce4(const float* __restrict__ 
     }
 }
 
-#ifndef CTMI_LN_BWD_BLOCKS
-#define CTMI_LN_BWD_BLOCKS 256      // one workgroup per CU: same-box A/B vs 512: 31.0 -> 21.4 us at [8192,1024] bf16 (half the end-of-kernel LDS combines and partial rows)
-#endif
-static const int LN_BWD_MAX_BLOCKS = 512;                               // workspace sizing (fixed); the launch uses CTMI_LN_BWD_BLOCKS <= this
+constexpr int LN_BWD_BLOCKS = 256;          // one workgroup per CU: same-box A/B vs 512: 31.0 -> 21.4 us at [8192,1024] bf16 (half the end-of-kernel LDS combines and partial rows)
+static const int LN_BWD_MAX_BLOCKS = 512;                               // workspace sizing (fixed); the launch uses LN_BWD_BLOCKS <= this
 extern "C" int64_t ctmi_layernorm_bwd_ws(int64_t rows, int64_t cols) {
     (void)rows;
     return (int64_t)LN_BWD_MAX_BLOCKS * 4 * cols;          // up to 4 partial rows per block (dw, db, colsum(dres), colsum(dx))
@@ -468,7 +462,7 @@ static int ln_bwd_parts(const void* dy, const void* x, const float* w, const flo
     if (vec_ok) {
         const int mv = cols <= 64 * VEC ? 1 : (cols <= 2 * 64 * VEC ? 2 : (cols <= 4 * 64 * VEC ? 4 : 8));
         const int nw = lnb_waves(mv);
-        int grid = (int)std::min<int64_t>(cdiv64(rows, nw), CTMI_LN_BWD_BLOCKS);
+        int grid = (int)std::min<int64_t>(cdiv64(rows, nw), LN_BWD_BLOCKS);
         if (mv >= 4) {                                                  // wide rows: one workgroup per row, columns split over 4 waves
             grid = (int)std::min<int64_t>(rows, LN_BWD_MAX_BLOCKS);
             if (mv == 4) hipLaunchKernelGGL((ln_bwd_wide<T, 1>), dim3(grid), dim3(256), 0, st, (const T*)dy, (const T*)x, w, mean, rstd, (const T*)dres, (T*)dx, ws, rows, (int)cols);

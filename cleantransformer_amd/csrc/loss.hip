@@ -13,13 +13,6 @@ __device__ __forceinline__ int64_t ce_target(const int64_t* labels, int64_t row,
     return (t == ignore) ? -1 : t;
 }
 
-// combine two (max, sum) online-softmax states
-__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
-    const float mn = fmaxf(m, m2);
-    s = s * __expf(m - mn) + s2 * __expf(m2 - mn);
-    m = mn;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void ce_fwd_k(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
                                                 float* __restrict__ row_lse, float* __restrict__ row_loss,

@@ -5,6 +5,14 @@
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
+// Hardware-transpose LDS read (ds_read_b64_tr_b16) through the compiler builtin, so hipcc tracks its lgkmcnt itself: lane i of a 16-lane
+// group addresses row R0 + (i>>2), columns C0 + 4*(i&3).. of a row-major 16-bit tile and receives column C0 + i for rows R0..R0+3
+// (probe-verified) — the operand that an MFMA contracts over the tile's ROW index, with no transposed copy staged anywhere.
+__device__ __forceinline__ uint2 lds_read_tr_b16(const void* p) {
+    typedef __attribute__((address_space(3))) short4_t lds_v4;
+    return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(unsigned)(size_t)p));
+}
+
 template <typename T> struct Mma;
 template <> struct Mma<bf16_t> {
     static constexpr int K = 32, KL = 8;

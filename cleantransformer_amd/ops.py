@@ -148,20 +148,7 @@ def side_stream(device) -> "torch.cuda.Stream":
     the dgrad / attention-backward chain (they feed nothing downstream in backward)."""
     st = _SIDE_STREAMS.get(device)
     if st is None:
-        prio = os.environ.get("CTMI_SIDE_STREAM_PRIORITY")               # "low" / "high" / an integer: hipStreamCreateWithPriority (experiments)
-        if prio is None:
-            st = torch.cuda.Stream(device=device)
-        else:
-            hip = C.CDLL("libamdhip64.so")
-            lo, hi = C.c_int(0), C.c_int(0)
-            hip.hipDeviceGetStreamPriorityRange(C.byref(lo), C.byref(hi))   # least, greatest (numerically: greatest priority is the smaller number)
-            val = lo.value if prio == "low" else (hi.value if prio == "high" else int(prio))
-            h = C.c_void_p()
-            with torch.cuda.device(device):
-                if hip.hipStreamCreateWithPriority(C.byref(h), C.c_uint(1), C.c_int(val)) != 0:
-                    raise _lib.CtmiError("hipStreamCreateWithPriority failed")
-            st = torch.cuda.ExternalStream(h.value, device=device)
-            st._ctmi_priority = (val, lo.value, hi.value)
+        st = torch.cuda.Stream(device=device)
         _SIDE_STREAMS[device] = st
     return st
 

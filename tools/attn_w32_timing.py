@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Per-wave cycle anatomy of the 256-row attention forward (variant build -DCTMI_W32_TIMING=1): matrix segments, vector segments and
-the barrier waits behind each, from s_memtime deltas the kernel dumps over stat_l.  Usage: python tools/attn_w32_timing.py"""
+the barrier waits behind each, from s_memtime deltas the kernel dumps over stat_l.  Usage: python tools/attn_w32_timing.py
+
+Needs tools/experiments/attn_w32_timing.patch applied first (`git apply tools/experiments/attn_w32_timing.patch`): the instrumentation is
+not part of csrc/attention_w32.hip.  Without it the variant builds, but stat_l holds row sums, not cycle counts."""
 import os
 import sys
 
