@@ -26,7 +26,8 @@ __global__ __launch_bounds__(256) void ce_fwd_k(const T* __restrict__ logits, in
         for (int64_t c = Cv + threadIdx.x; c < C; c += 256) {
             const float v = Cvt<T>::to_f(x[c]);
             const float mn = fmaxf(m, v);
-            s = s * __expf(m - mn) + __expf(v - mn);
+            const float ms = (mn == -INFINITY) ? 0.f : mn;
+            s = s * __expf(m - ms) + __expf(v - ms);
             m = mn;
         }
         for (int64_t c = (int64_t)threadIdx.x * VEC; c < Cv; c += 256 * VEC) {
@@ -36,21 +37,25 @@ __global__ __launch_bounds__(256) void ce_fwd_k(const T* __restrict__ logits, in
 #pragma unroll
             for (int j = 1; j < VEC; ++j) vm = fmaxf(vm, v[j]);
             const float mn = fmaxf(m, vm);
+            const float ms = (mn == -INFINITY) ? 0.f : mn;
             float add = 0.f;
 #pragma unroll
-            for (int j = 0; j < VEC; ++j) add += __expf(v[j] - mn);
-            s = s * __expf(m - mn) + add;
+            for (int j = 0; j < VEC; ++j) add += __expf(v[j] - ms);
+            s = s * __expf(m - ms) + add;
             m = mn;
         }
     } else {
         for (int64_t c = threadIdx.x; c < C; c += 256) {
             const float v = Cvt<T>::to_f(x[c]);
             const float mn = fmaxf(m, v);
-            s = s * __expf(m - mn) + __expf(v - mn);
+            const float ms = (mn == -INFINITY) ? 0.f : mn;
+            s = s * __expf(m - ms) + __expf(v - ms);
             m = mn;
         }
     }
-    // threads that saw nothing hold (m=-inf, s=0): __expf(-inf - mn) = 0 keeps them neutral as long as mn is finite
+    // threads that saw nothing hold (m=-inf, s=0): __expf(-inf - mn) = 0 keeps them neutral as long as mn is finite.  A trip whose classes
+    // are all -inf (a masked vocabulary slice) on such a state has mn = -inf: `ms` subtracts 0 there instead (one select per trip), so the
+    // entries add __expf(-inf) = 0 and the state stays (-inf, 0) instead of turning into NaN.  A row that is -inf everywhere stays undefined.
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
@@ -218,7 +223,8 @@ __global__ __launch_bounds__(1024) void ce_fused_k(const T* __restrict__ logits,
     for (int64_t c = Cv + threadIdx.x; c < C; c += NT) {
         const float v = Cvt<T>::to_f(x[c]);
         const float mn = fmaxf(m, v);
-        s = s * __expf(m - mn) + __expf(v - mn);
+        const float ms = (mn == -INFINITY) ? 0.f : mn;
+        s = s * __expf(m - ms) + __expf(v - ms);
         m = mn;
     }
     int64_t i = threadIdx.x;
@@ -235,12 +241,13 @@ __global__ __launch_bounds__(1024) void ce_fused_k(const T* __restrict__ logits,
             for (int j = 0; j < VEC; ++j) vm = fmaxf(vm, v[u][j]);
         }
         const float mn = fmaxf(m, vm);
+        const float ms = (mn == -INFINITY) ? 0.f : mn;
         float add = 0.f;
 #pragma unroll
         for (int u = 0; u < UNR; ++u)
 #pragma unroll
-            for (int j = 0; j < VEC; ++j) add += __expf(v[u][j] - mn);
-        s = s * __expf(m - mn) + add;
+            for (int j = 0; j < VEC; ++j) add += __expf(v[u][j] - ms);
+        s = s * __expf(m - ms) + add;
         m = mn;
     }
     for (; i < nvec; i += NT) {
@@ -250,10 +257,11 @@ __global__ __launch_bounds__(1024) void ce_fused_k(const T* __restrict__ logits,
 #pragma unroll
         for (int j = 1; j < VEC; ++j) vm = fmaxf(vm, v[j]);
         const float mn = fmaxf(m, vm);
+        const float ms = (mn == -INFINITY) ? 0.f : mn;
         float add = 0.f;
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) add += __expf(v[j] - mn);
-        s = s * __expf(m - mn) + add;
+        for (int j = 0; j < VEC; ++j) add += __expf(v[j] - ms);
+        s = s * __expf(m - ms) + add;
         m = mn;
     }
 #pragma unroll

@@ -398,7 +398,7 @@ __global__ __launch_bounds__(256) void sumsq_k(const float* __restrict__ x, int6
 }
 extern "C" int ctmi_sumsq(const float* x, int64_t n, double* out, int accumulate, void* stream) {
     ProfScope prof__(CTMI_PROF_OTHER, as_stream(stream));
-    CTMI_REQUIRE(x && out && n >= 0, "sumsq: bad args");
+    CTMI_REQUIRE(out && n >= 0 && (x || n == 0), "sumsq: bad args");      // an empty torch tensor has a null data pointer
     hipStream_t st = as_stream(stream);
     if (!accumulate) { if (hipMemsetAsync(out, 0, sizeof(double), st) != hipSuccess) { ctmi_set_error("sumsq: memset failed"); return CTMI_ERR_LAUNCH; } }
     if (n == 0) return CTMI_OK;

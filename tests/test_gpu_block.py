@@ -295,6 +295,47 @@ def test_block_one_call_equals_per_op_sequence(dtype, post, B, S, H, nh):
         assert torch.equal(a, b)                                                # one stream or two: same bits
 
 
+@pytest.mark.parametrize("post", [False, True])
+@pytest.mark.parametrize("dtype,B,S,H,nh", [(torch.float32, 10, 256, 64, 8), (torch.bfloat16, 10, 256, 64, 8), (torch.bfloat16, 9, 256, 1024, 16)],
+                         ids=["fp32-T2560-H64", "bf16-T2560-H64", "bf16-T2304-H1024"])
+def test_block_bias_sums_from_the_layernorm_backward_with_several_rows_per_wave(dtype, post, B, S, H, nh):
+    """bd and b2 come out of the LayerNorm backward of the one-call form (ln_bwd_vec with NS = 4: per-lane column sums of the residual gradient it
+    reads and of the dx it stores).  That kernel launches at most 256 workgroups x 8 waves = 2048 waves, so only T > 2048 makes a wave sum a
+    SECOND row into those accumulators: T = 2560 at H = 64 (one 16-byte chunk per lane, guarded in bf16 / FULL in fp32) and T = 2304 at H = 1024
+    (the shipped bf16 instantiation: two chunks per lane, FULL).  Same construction and bounds as test_block_one_call_equals_per_op_sequence,
+    except for bd / b2: both sides are fp32 sums of the SAME T stored values in another order, so they differ by rounding only — typically
+    sqrt(T) * 2^-24 of the partial sums; the bound is 4 * T * 2^-24 * max|ref|.  One row's contribution is about max|ref| / (3 sqrt(T)): ten times
+    that bound at these T, where the sqrt(T)-sized bound of the other test lets a hundred rows through."""
+    o = ops()
+    T = B * S
+    x, dout, params, mask, slopes, _, _ = _block_inputs(B, S, H, nh, dtype, seed=B * 1000 + S + H, pad="right")
+    eps = 1e-5
+    acts = o.bloom_block_fwd(x, params, mask, slopes, eps, post, B, S, nh)
+    ref = EMU.bloom_block_fwd(x, params, mask, slopes, eps, post, B, S, nh, K=o)
+    assert torch.equal(acts.out, ref.out)
+    dx, grads = o.bloom_block_bwd(acts, x, params, mask, slopes, eps, post, dout)
+    dx_ref, g_ref = EMU.bloom_block_bwd(ref, x, params, mask, slopes, eps, post, dout, K=o)
+    torch.cuda.synchronize()
+    rt = 2e-5 if dtype == torch.float32 else 2e-2
+    grouped = dtype != torch.float32 and H % 256 == 0 and T % 32 == 0 and T >= 64 and os.environ.get("CTMI_WGRAD_GROUP", "1") != "0"
+    assert relerr(dx, dx_ref) < rt
+    for n, g, gr in zip(lib().BLK_PARAMS, grads, g_ref):
+        if n in ("bd", "b2"):
+            err, bound = float((g - gr).abs().max()), 4 * T * 2.0 ** -24 * float(gr.abs().max())
+            if os.environ.get("CTMI_TEST_VERBOSE"):
+                print(f"[block bias sums] {n} T={T} H={H} post={post}: max |g - g_ref| {err:.3e}, bound {bound:.3e}, max |g_ref| {float(gr.abs().max()):.3e}")
+            assert torch.isfinite(g).all() and err <= bound, (n, err, bound)
+        elif n in ("w2", "w1", "b1") and not grouped:
+            assert torch.equal(g, gr), n
+        elif n in ("w2", "w1"):
+            assert relerr(g, gr) < 5e-6, n
+        elif n in ("bqkv", "b1"):
+            scale = float(gr.abs().max()) + 1e-30
+            assert float((g - gr).abs().max()) <= (2e-5 if dtype == torch.float32 else 2e-2) * scale * math.sqrt(T), n
+        else:
+            assert relerr(g, gr) < rt, n
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("B,S,H,nh", [(2, 16, 64, 8), (2, 96, 256, 4), (2, 256, 1024, 16)])
 def test_block_gpt2_spelling_with_in_out_weights(dtype, B, S, H, nh):
