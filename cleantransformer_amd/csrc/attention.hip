@@ -454,12 +454,17 @@ __global__ __launch_bounds__(256, ATTN_MINW) void attn_fwd_kernel(AttnP p) {
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) mx = max3f(max3f(mx, x[nt][0], x[nt][1]), x[nt][2], x[nt][3]);
         mx = group_max4(mx);
-        const float m_new = fmaxf(m, mx);                                   // finite: every tile holds >= 1 real key
-        const float alpha = __expf(m - m_new);
+        const float m_new = fmaxf(m, mx);                                   // finite without an additive mask: every tile holds >= 1 real key
+        // An additive mask may be -inf on every key a row has met so far (a band or sliding-window mask, left padding written as -inf):
+        // the running maximum is then still -inf and `x - m_new` would be -inf - -inf.  Subtract 0 instead, one select per tile (as
+        // ce_fwd_k does): such a row's probabilities are exp(-inf) = 0, alpha = exp(-inf - 0) = 0 scales sums that are still 0.
+        float m_sub = m_new;
+        if constexpr (AM) m_sub = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = __expf(m - m_sub);
         f32x4 rs4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-            const f32x4 e4 = (x[nt] - m_new) * 1.4426950408889634f;           // (s - m) first: finfo.min - finfo.min must be 0, not inf - inf
+            const f32x4 e4 = (x[nt] - m_sub) * 1.4426950408889634f;           // (s - m) first: finfo.min - finfo.min must be 0, not inf - inf
             f32x4 p4;
 #pragma unroll
             for (int r = 0; r < 4; ++r) p4[r] = __builtin_amdgcn_exp2f(e4[r]);
